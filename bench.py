@@ -8,10 +8,17 @@ unfreeze_strategy=brain_encoder (Adam over the brain encoder; the frozen w2v sti
 gradients, as the reference does). One step = Trainer.train_step (train/train_loop.py, the step
 run.py executes; reference src/train/train_loop.py:41-84): forward + backward + DDP gradient
 all-reduce (N>1) + Adam, replayed as a captured HIP graph, plus the CTC loss readback (into pinned
-host memory, stream-ordered), inputs pre-staged in HBM. N=1 base runs add a nested record for the
-north-star target (configs[2], Conformer-large bs=32) with its own parity and CPU baseline.
+host memory, stream-ordered), inputs pre-staged in HBM.
 
-usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, one
+JSON result line. --dump-outputs DIR also writes what the last timed step computed (DIR/<name>.npy,
+float32; the inputs, weights and dropout seeds are fixed, so two builds can be compared output for
+output). --full adds everything else: the GEMM roofline pass, parity against the CPU oracle, the CPU
+baseline and, on N=1 base runs, the nested records for the north-star target (configs[2],
+Conformer-large bs=32, with its own parity and CPU baseline), configs[3] / configs[4], the train
+evaluator and the exact-fp32 mode; the --no-* options drop single legs of a --full run.
+
+usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        N>1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -243,10 +250,37 @@ def experiment_for(kind, model):
     return SyntheticStepExperiment(model, lr=1e-3)
 
 
-def timed_run(kind, args, world, rank, device, use_graph, steps=None, warmup=None, evaluator=None, roofline=None):
+DUMP_BUDGET = 60_000_000   # bytes --dump-outputs may write in all (under 64 MB with the .npy headers)
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET):
+    """Writes each tensor of `arrays` as out_dir/<name>.npy in float32. The arrays share `budget` bytes
+    equally; one that is larger than its share is written as a fixed sample of it (flat indices drawn
+    with seed 0, sorted: the same elements in every run and every build)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // 4 // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, share))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def step_outputs(out, losses, trainer):
+    """What a caller of the timed path holds after its last step: the step's ModelOutput (CTC loss,
+    logits), the loss of every timed step, and the parameters the optimizer has updated."""
+    params = [p.detach().reshape(-1).float() for g in trainer.optimizer.param_groups for p in g["params"]]
+    return {"loss": out.loss.reshape(1), "logits": out.logits, "timed_step_losses": losses,
+            "optimized_params": torch.cat(params)}
+
+
+def timed_run(kind, args, world, rank, device, use_graph, steps=None, warmup=None, evaluator=None, roofline=None,
+              dump=None):
     """W warm-up steps + K timed steps of the Trainer's training step (train/train_loop.py, the step
-    run.py executes) on the workload, then the GEMM-timing pass. Graph mode: the first W steps run
-    eagerly, the next one captures the step (untimed), the K timed steps are replays."""
+    run.py executes) on the workload, then (dump: a directory) the last step's outputs written there
+    and (roofline) the GEMM-timing pass. Graph mode: the first W steps run eagerly, the next one
+    captures the step (untimed), the K timed steps are replays."""
     import argparse as _ap
     from wav2vec2forbrain_amd import functional as Fn, _lib
     from wav2vec2forbrain_amd.train.train_loop import Trainer
@@ -297,13 +331,16 @@ def timed_run(kind, args, world, rank, device, use_graph, steps=None, warmup=Non
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss_host[i].copy_(metrics(trainer.train_step(batch)), non_blocking=True)
+        out = trainer.train_step(batch)
+        loss_host[i].copy_(metrics(out), non_blocking=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     replayed = trainer.graph_steps - g0
     Fn.check_gru_status()   # a multi-CU GRU timeout in any timed step raises here
+    if dump and rank == 0:
+        write_outputs(dump, step_outputs(out, loss_host[:, 0], trainer))
     # GEMM roofline: HIP events around every GEMM launch of the same number of eager Trainer steps,
     # right after the timed region (a captured graph cannot carry per-launch events); the kernels and
     # their shapes are the ones the graph replays.
@@ -361,6 +398,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bs", type=int, default=32)
     ap.add_argument("--seq", type=int, default=1024)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, the timed steps' losses, the "
+                         "updated parameters) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the GEMM roofline pass, the parity check, the CPU baseline "
+                         "and (N=1 base runs) the nested records; the --no-* options below drop single legs of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-roofline", action="store_true",
@@ -376,11 +419,20 @@ def main():
     ap.add_argument("--config", choices=["base", "conformer", "large"], default="base",
                     help="base = BASELINE configs[1] (headline); conformer = configs[2]; large = configs[3] per GPU")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the timed steps and the result line only
+        args.no_cpu_baseline = args.no_parity = args.no_roofline = args.no_conformer = args.no_extra = True
     # the committed tree carries sources only: build the library before the first HIP call
     from wav2vec2forbrain_amd import build_lib
-    build_lib.ensure_built()
+    try:
+        build_lib.ensure_built()
+    except PermissionError as e:
+        # a tree another user built and this one cannot write to (no lock file, no objects): run on the
+        # library that is there; without one there is nothing to run
+        if not os.path.exists(build_lib.LIB):
+            raise
+        log(f"cannot build in this tree ({e}); using {build_lib.LIB} as it is")
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # B2P_DIST_BACKEND=gloo (with more ranks than GPUs, ranks share devices) rehearses the N>1 path
@@ -405,7 +457,7 @@ def main():
     Fn.set_precision("bf16")
     use_graph = True if args.graph is None else bool(args.graph)
 
-    r = timed_run(args.config, args, world, rank, device, use_graph)
+    r = timed_run(args.config, args, world, rank, device, use_graph, dump=args.dump_outputs)
     if rank != 0:
         dist.destroy_process_group() if world > 1 else None
         return
@@ -437,8 +489,9 @@ def main():
         "step_mode": r["step_mode"] + " of Trainer.train_step (train/train_loop.py, the step run.py runs)",
         "samples_per_s": round(steps_per_s * args.bs, 2),
         "step_mfma_frac": round(step_tflop * steps_per_s / world / BF16_DENSE_PEAK_TFLOPS, 4),
-        "roofline": roofline_record(r["gemm"], args.config),
     }
+    if args.full:
+        res["roofline"] = roofline_record(r["gemm"], args.config)
     if args.config == "conformer":
         res["metric"] = "train steps/sec + CTC loss, b2p2t_gru+w2v_conformer bs=32 seq=1024"
     elif args.config == "large":

@@ -16,5 +16,5 @@ timeout -k 10 600 python3 -u -m pytest -x -q --timeout 300 --timeout-method thre
 tail -1 $O/tests.log
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-conformer --no-extra > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-conformer --no-extra > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 -c "import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print('base', d['value'], d['ms_per_step'], d['roofline']['frac'], d['parity']['max_rel_err'])"

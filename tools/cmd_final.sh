@@ -8,7 +8,7 @@ T=${1:-final}
 [ "${SKIP_REHEARSAL:-0}" = 1 ] || bash tools/cmd_rehearsal.sh $T || exit 1
 mkdir -p gpurun_out/$T
 O=gpurun_out/$T
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline \
   --no-parity --no-conformer --no-extra > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
 python3 tools/prof_summary.py $O/prof 6 40 > $O/prof_summary_base.txt 2>&1
 python3 - "$O" <<'PY' >> $O/prof_summary_base.txt

@@ -9,7 +9,7 @@ rc=$?; tail -3 $O/pytest.log; echo "pytest wall $((SECONDS - T0)) s"; [ $rc -ne 
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 T0=$SECONDS
-timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 echo "bench wall $((SECONDS - T0)) s" | tee $O/bench_wall.txt
 python3 -c "
 import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1])

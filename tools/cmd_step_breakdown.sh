@@ -5,7 +5,7 @@ set -u
 # usage: bash tools/cmd_step_breakdown.sh <tag>
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$1; mkdir -p $O
-timeout -k 10 300 rocprofv3 --kernel-trace -d $O/tb -o kt -- python3 bench.py --steps 8 --warmup 3 --no-cpu-baseline \
+timeout -k 10 300 rocprofv3 --kernel-trace -d $O/tb -o kt -- python3 bench.py --full --steps 8 --warmup 3 --no-cpu-baseline \
   --no-parity --no-roofline --no-conformer > $O/base.log 2>&1 || { tail -20 $O/base.log; exit 1; }
 python3 tools/step_breakdown.py $O/tb 8 40 > $O/base_replay_step.txt 2>&1; head -3 $O/base_replay_step.txt
 timeout -k 10 300 rocprofv3 --kernel-trace -d $O/tc -o kt -- python3 bench.py --config conformer --steps 8 --warmup 3 \

@@ -110,19 +110,33 @@ def build(verbose: bool = False, jobs: int | None = None) -> str:
 def ensure_built() -> str:
     """The hook every GPU entry point (tests/conftest.py, bench.py, __graft_entry__.smoke) runs before
     its first HIP call: the committed tree carries sources only (the .so is git-ignored), so a fresh
-    checkout builds here. Compilation runs in hipcc child processes; nothing here touches the GPU."""
+    checkout builds here. Compilation runs in hipcc child processes; nothing here touches the GPU.
+    A current library is returned without writing anything (no build/ directory, no lock file), so a
+    tree that another user built and this one may only read still runs."""
+    if _current(*_stamps()):
+        return LIB
     return build(verbose=True)
 
 
-def _build_locked(verbose: bool, jobs: int | None) -> str:
+def _stamps():
+    """(sources, their stamps, the library's stamp) for the tree as it is."""
     import hashlib
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")))
     hh = _headers_hash()
     shas = [_src_hash(s, hh) for s in srcs]
     lib_sha = hashlib.sha256("".join(os.path.basename(s) + ":" + h + ";" for s, h in zip(srcs, shas)).encode()).hexdigest()
+    return srcs, shas, lib_sha
+
+
+def _current(srcs, shas, lib_sha) -> bool:
     # a library whose stamp matches is current even without the objects (a snapshot that carries the
     # built .so but not build/)
-    if os.path.exists(LIB) and _stamp(LIB_STAMP) == lib_sha:
+    return os.path.exists(LIB) and _stamp(LIB_STAMP) == lib_sha
+
+
+def _build_locked(verbose: bool, jobs: int | None) -> str:
+    srcs, shas, lib_sha = _stamps()
+    if _current(srcs, shas, lib_sha):
         return LIB
     # the GPU box reports the whole machine's CPUs; its share is 16
     jobs = jobs or min(16, os.cpu_count() or 4)
