@@ -1,6 +1,6 @@
 """GEMM A/B on the base step's encoder shapes (bf16 operands, the epilogues the step uses): mean launch
 time and TF/s per shape under the current B2P_GEMM16_* environment. Run once per setting:
-    B2P_GEMM16_TALL=0 python tools/gemm_ab.py ; B2P_GEMM16_TALL=1 python tools/gemm_ab.py"""
+    B2P_GEMM16_PP192=0 python tools/gemm_ab.py ; B2P_GEMM16_PP192=1 python tools/gemm_ab.py"""
 import os
 import sys
 

@@ -576,7 +576,7 @@ __global__ void __launch_bounds__(256) ln_rot16_k(const float* __restrict__ x, c
 }
 
 constexpr int LN_BWD_ROWS = 16;   // rows per block (4 per wave): ~500 blocks at 8k rows
-// PF: prefetch the next row (B2P_LN_PREFETCH, default 1). MODE bits: 1 = dx_accum, 2 = dx_accum2, 4 = dxd
+// PF: prefetch the next row (the only form instantiated). MODE bits: 1 = dx_accum, 2 = dx_accum2, 4 = dxd
 // (compile-time, so a form holds registers only for the streams it reads: all three at once would not
 // fit two waves per SIMD)
 constexpr int LNB_A1 = 1, LNB_A2 = 2, LNB_DXD = 4;
@@ -1202,20 +1202,18 @@ namespace {
 typedef void (*LnBwdKernel)(const float*, const float*, const float*, const float*, const float*, float*, const float*,
                             float*, int64_t, int, uint32_t, float, uint64_t, float, float*, uint32_t, float, uint64_t,
                             uint16_t*, const uint64_t*, const float*);
-template <bool PF>
-LnBwdKernel ln_bwd_pick(int mode) {
+LnBwdKernel ln_bwd_kernel(int mode) {
   switch (mode) {
-    case 0: return ln_bwd_k<PF, 0>;
-    case 1: return ln_bwd_k<PF, 1>;
-    case 2: return ln_bwd_k<PF, 2>;
-    case 3: return ln_bwd_k<PF, 3>;
-    case 4: return ln_bwd_k<PF, 4>;
-    case 5: return ln_bwd_k<PF, 5>;
-    case 6: return ln_bwd_k<PF, 6>;
-    default: return ln_bwd_k<PF, 7>;
+    case 0: return ln_bwd_k<true, 0>;
+    case 1: return ln_bwd_k<true, 1>;
+    case 2: return ln_bwd_k<true, 2>;
+    case 3: return ln_bwd_k<true, 3>;
+    case 4: return ln_bwd_k<true, 4>;
+    case 5: return ln_bwd_k<true, 5>;
+    case 6: return ln_bwd_k<true, 6>;
+    default: return ln_bwd_k<true, 7>;
   }
 }
-LnBwdKernel ln_bwd_kernel(bool pf, int mode) { return pf ? ln_bwd_pick<true>(mode) : ln_bwd_pick<false>(mode); }
 }  // namespace
 
 extern "C" int64_t b2p_layernorm_bwd_workspace(int64_t rows, int64_t cols) {
@@ -1243,9 +1241,8 @@ extern "C" int b2p_layernorm_bwd_acc2(const float* dy, const float* x, const flo
   if (rows <= 0) return 0;
   const int nblk = (int)((rows + LN_BWD_ROWS - 1) / LN_BWD_ROWS);
   hipStream_t st = (hipStream_t)stream;
-  static const bool pf = getenv("B2P_LN_PREFETCH") ? atoi(getenv("B2P_LN_PREFETCH")) != 0 : true;
   const int mode = (dx_accum ? LNB_A1 : 0) | (dx_accum2 ? LNB_A2 : 0) | (dx_dropped ? LNB_DXD : 0);
-  hipLaunchKernelGGL(ln_bwd_kernel(pf, mode), dim3(nblk), dim3(256), 0, st, dy, x, gamma, mean, rstd, dx, dx_accum, workspace,
+  hipLaunchKernelGGL(ln_bwd_kernel(mode), dim3(nblk), dim3(256), 0, st, dy, x, gamma, mean, rstd, dx, dx_accum, workspace,
                      rows, (int)cols, b2p_dropout_threshold(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f,
                      drop_seed, drop_p, dx_dropped, b2p_dropout_threshold(in_drop_p),
                      in_drop_p > 0.f ? 1.f / (1.f - in_drop_p) : 1.f, in_drop_seed, d16, b2p_seed_epoch(), dx_accum2);

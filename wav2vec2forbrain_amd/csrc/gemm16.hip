@@ -21,12 +21,12 @@
 #include "gemm16_impl.inc"
 #include <algorithm>
 
-// row-tile band of the grouped tile order (tile_of); B2P_GEMM16_GROUP / B2P_GEMM16_GROUP_PP override
-static int gemm16_group(bool pp) {
-  static const int g_small = getenv("B2P_GEMM16_GROUP") ? atoi(getenv("B2P_GEMM16_GROUP")) : 0;
-  static const int g_pp = getenv("B2P_GEMM16_GROUP_PP") ? atoi(getenv("B2P_GEMM16_GROUP_PP")) : 0;
-  return pp ? g_pp : g_small;
-}
+// row-tile band of the grouped tile order (tile_of): 0, the kernels' own default, for every family
+constexpr int GEMM16_GROUP = 0;
+// a k-contiguous launch of at least this many 256 x 256 tiles takes the ping-pong kernel at K >= 512
+constexpr int GEMM16_PP_TILES = 360;
+// the narrow ping-pong kernels take k-contiguous launches up to this N
+constexpr int GEMM16_PN_MAX_N = 2048;
 
 // epilogue kind of a launch (gemm16_impl.inc: EK_*); EK_GENERIC where the fast kinds' assumptions fail
 static uint32_t epi_kind(const b2p_gemm_desc& d, const EpiArgs& ea) {
@@ -66,16 +66,6 @@ bool gemm16_splitk_fused(const b2p_gemm_desc& d) {
   const int64_t nz = (int64_t)d.nz1 * d.nz2;
   const int64_t need = (int64_t)d.ksplit * nz * d.M * d.N + ((d.M + 127) / 128) * ((d.N + 127) / 128) * nz;
   return v4 && d.workspace_floats >= need;
-}
-
-// Kernel variant knob (b2p_gemm16_variant, B2P_GEMM16_VARIANT; A/B tools), bits: 1 = the 256-column ping-pong
-// kernel without the quarter-scheduled DMA, 2 = no narrow ping-pong kernel (those launches on 128 x 128)
-static int g_variant = getenv("B2P_GEMM16_VARIANT") ? atoi(getenv("B2P_GEMM16_VARIANT")) : 0;
-int gemm16_variant_get() { return g_variant; }
-extern "C" int b2p_gemm16_variant(int v) {
-  const int old = g_variant;
-  if (v >= 0) g_variant = v;
-  return old;
 }
 
 static int run(const b2p_gemm_desc& d, hipStream_t st, int fam, uint32_t ek, unsigned nwg, int tm, int tn, int grp) {
@@ -123,9 +113,8 @@ int b2p_gemm16_launch(const b2p_gemm_desc& d, hipStream_t st) {
   // does a split-K launch of >= 1024-deep slices (the weight gradients, K = tokens).
   // Round 4 (register epilogue, tools/gemm_ab.py): a k-contiguous launch of >= 360 256 x 256 tiles (~1.5
   // rounds of the CUs: N >= 3072 at 7968 tokens) also runs faster on it, at K = 768 / 1024
-  // (B2P_GEMM16_PP_TILES).
+  // (GEMM16_PP_TILES).
   static int pp_mode = getenv("B2P_GEMM16_PP") ? atoi(getenv("B2P_GEMM16_PP")) : 1;
-  static int pp_tiles = getenv("B2P_GEMM16_PP_TILES") ? atoi(getenv("B2P_GEMM16_PP_TILES")) : 360;
   const int64_t tiles_pp = ((d.M + 255) / 256) * ((d.N + 255) / 256) * nz;
   const int64_t kper = ks > 1 ? (int64_t)d.kchunk : d.K;
   const bool nt = d.A.inner_is_k && d.B.inner_is_k;
@@ -138,7 +127,7 @@ int b2p_gemm16_launch(const b2p_gemm_desc& d, hipStream_t st) {
   const bool pp = !d.A.conv && (!h16 || nt) && ext_ok(d.A, d.M) && ext_ok(d.B, d.N) &&
                   (pp_mode == 2 || (pp_mode == 1 && ((tiles_pp >= 192 && kper >= 2048) ||
                                                      (ks > 1 && tiles_pp >= 160 && kper >= 1024) ||
-                                                     (nt && tiles_pp >= pp_tiles && kper >= 512))));
+                                                     (nt && tiles_pp >= GEMM16_PP_TILES && kper >= 512))));
   if (pp) {
     const int tm = (int)((d.M + 255) / 256), tn = (int)((d.N + 255) / 256);
     // 192 x 256 tiles (B2P_GEMM16_PP192: 0 off, 1 (default) when fewer rounds of the 256 CUs x tile rows
@@ -149,25 +138,23 @@ int b2p_gemm16_launch(const b2p_gemm_desc& d, hipStream_t st) {
       const int64_t t3 = (int64_t)tm3 * tn * nz;
       const int64_t cost256 = (tiles_pp + 255) / 256 * 256, cost192 = (t3 + 255) / 256 * 192;
       if (pp192 == 2 || cost192 * 100 <= cost256 * 92)
-        return run(d, st, G16_PP192, ek, (unsigned)t3, tm3, tn, gemm16_group(true));
+        return run(d, st, G16_PP192, ek, (unsigned)t3, tm3, tn, GEMM16_GROUP);
     }
-    return run(d, st, G16_PP, ek, (unsigned)tiles_pp, tm, tn, gemm16_group(true));
+    return run(d, st, G16_PP, ek, (unsigned)tiles_pp, tm, tn, GEMM16_GROUP);
   }
-  // narrow ping-pong tiles, PBM x 128 (B2P_GEMM16_PN: 0 off, 1 (default) for k-contiguous launches with
-  // N <= B2P_GEMM16_PN_MAX_N, 2 for every k-contiguous launch): 192 rows where fewer CU-rounds x tile rows come out of it
+  // narrow ping-pong tiles, PBM x 128, for k-contiguous launches with N <= GEMM16_PN_MAX_N: 192 rows where
+  // fewer CU-rounds x tile rows come out of it
   // (N = 768: 252 tiles in one round), else 256 (N = 1024: 256 tiles); the LDS-staged (GENERIC) epilogue
   // stays on the other kernels
   // N <= 2048 (round 6, tools/gemm_ab.py, profiles/r06o_pn_wide_ab.txt): the Conformer's pointwise conv 1
   // (7968 x 2048 x 1024) 56.2 -> 49.8 us; the QKV projection (N = 2304) is slower on it (53.8 -> 57.2 us)
-  static int pn_mode = getenv("B2P_GEMM16_PN") ? atoi(getenv("B2P_GEMM16_PN")) : 1;
-  static int pn_max_n = getenv("B2P_GEMM16_PN_MAX_N") ? atoi(getenv("B2P_GEMM16_PN_MAX_N")) : 2048;
-  if (pn_mode && !(gemm16_variant_get() & 2) && nt && !d.A.conv && ek != EK_GENERIC && ext_ok(d.A, d.M) && ext_ok(d.B, d.N) &&
-      (ks == 1 || d.kchunk % 64 == 0) && (pn_mode == 2 || d.N <= pn_max_n)) {
+  if (nt && !d.A.conv && ek != EK_GENERIC && ext_ok(d.A, d.M) && ext_ok(d.B, d.N) &&
+      (ks == 1 || d.kchunk % 64 == 0) && d.N <= GEMM16_PN_MAX_N) {
     const int tn = (int)((d.N + 127) / 128), tm2 = (int)((d.M + 255) / 256), tm3 = (int)((d.M + 191) / 192);
     const int64_t t256 = (int64_t)tm2 * tn * nz, t192 = (int64_t)tm3 * tn * nz;
     const int64_t cost256 = (t256 + 255) / 256 * 256, cost192 = (t192 + 255) / 256 * 192;
-    if (cost192 < cost256) return run(d, st, G16_PN192, ek, (unsigned)t192, tm3, tn, gemm16_group(true));
-    return run(d, st, G16_PN256, ek, (unsigned)t256, tm2, tn, gemm16_group(true));
+    if (cost192 < cost256) return run(d, st, G16_PN192, ek, (unsigned)t192, tm3, tn, GEMM16_GROUP);
+    return run(d, st, G16_PN256, ek, (unsigned)t256, tm2, tn, GEMM16_GROUP);
   }
   const int tm = (int)((d.M + 127) / 128), tn = (int)((d.N + 127) / 128);
   const int64_t nwg = (int64_t)tm * tn * nz;
@@ -179,23 +166,10 @@ int b2p_gemm16_launch(const b2p_gemm_desc& d, hipStream_t st) {
     b2p_set_error("gemm16: split-K chunk must be a multiple of 32");
     return 1;
   }
-  // 256 x 128 tiles (B2P_GEMM16_TALL: 0 off, 1 when the grid still gives every CU at least `tall_min`
-  // tiles of 256 x 128, default 2): plain or conv operands, any split
-  static int tall = getenv("B2P_GEMM16_TALL") ? atoi(getenv("B2P_GEMM16_TALL")) : 0;
-  static int tall_min = getenv("B2P_GEMM16_TALL_MIN") ? atoi(getenv("B2P_GEMM16_TALL_MIN")) : 512;
-  const int tmt = (int)((d.M + 255) / 256);
-  const int64_t nwg_t = (int64_t)tmt * tn * nz;
-  if (tall && nwg_t >= tall_min && !h16 && nt) {
-    return run(d, st, G16_TALL, ek, (unsigned)nwg_t, tmt, tn, gemm16_group(false));
-  }
-  // 128 x 128 x 64 two-stage tiles (B2P_GEMM16_K64: 0 never = default, 1 always, -1 for grids of < 512
-  // tiles). In isolation (tools/gemm_ab.py, L2-warm repeated launches; profiles/r03s_gemm_k64_ab.txt)
-  // the N = 768 encoder shapes and the 768 x 768 split-K weight gradient ran 7-15 % faster with -1, but
-  // inside the step (cold operands, side-stream concurrency) base and Conformer steps did not move
-  // (16.46 vs 16.44 ms, 88.2 vs 88.6 ms; profiles/r03t_k64_step_ab.txt), so the default stays off.
-  static int k64 = getenv("B2P_GEMM16_K64") ? atoi(getenv("B2P_GEMM16_K64")) : 0;
-  if ((k64 == 1 || (k64 < 0 && nwg < 512)) && (ks == 1 || d.kchunk % 64 == 0) && !h16 && nt) {
-    return run(d, st, G16_K64, ek, (unsigned)nwg, tm, tn, gemm16_group(false));
-  }
-  return run(d, st, G16_SMALL, ek, (unsigned)nwg, tm, tn, gemm16_group(false));
+  // Measured and removed: 256 x 128 four-wave tiles (never the default) and 128 x 128 x 64 two-stage tiles.
+  // In isolation (tools/gemm_ab.py, L2-warm repeated launches; profiles/r03s_gemm_k64_ab.txt) the N = 768
+  // encoder shapes and the 768 x 768 split-K weight gradient ran 7-15 % faster on the latter for grids of
+  // < 512 tiles, but inside the step (cold operands, side-stream concurrency) base and Conformer steps did
+  // not move (16.46 vs 16.44 ms, 88.2 vs 88.6 ms; profiles/r03t_k64_step_ab.txt).
+  return run(d, st, G16_SMALL, ek, (unsigned)nwg, tm, tn, GEMM16_GROUP);
 }

@@ -8,7 +8,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-int gemm16_variant_get();   // gemm16.hip, bits: 1 = the quarter-scheduled DMA off, 2 = the narrow kernel off (A/B)
 
 
 namespace {
@@ -639,13 +638,9 @@ struct Cfg {
   static constexpr int OCC = LDS > 80 * 1024 ? 1 : 2;           // workgroups per CU
 };
 using CfgSmall = Cfg<128, 128, 32, 3>;   // 4 waves, 3 workgroups/CU by LDS (48 KB) and VGPRs (143)
-// 256 x 128 tiles of 4 waves with 128 x 64 wave tiles (8 x 4 MFMA tiles): a quarter less operand traffic
-// per FLOP than 128 x 128 (1/256 + 1/128 vs 2/128 of K per output) and 12 fragment reads per 32 MFMAs
-// instead of 8 per 16; 72 KB of LDS, 2 workgroups per CU (B2P_GEMM16_TALL)
-using CfgTall = Cfg<256, 128, 32, 3, 128>;
-// 128 x 128 x 64 tiles, 2 stages (64 KB, 2 workgroups/CU): half the barriers per K (B2P_GEMM16_K64)
-using CfgK64 = Cfg<128, 128, 64, 2>;
-// Measured and removed (DESIGN.md "rejected"): 128 x 128 x 64 two-stage tiles (no gain inside the step),
+// Measured and removed (DESIGN.md "rejected"): 128 x 128 x 64 two-stage tiles (Cfg<128, 128, 64, 2>: half
+// the barriers per K, no gain inside the step), 256 x 128 tiles of 4 waves with 128 x 64 wave tiles
+// (Cfg<256, 128, 32, 3, 128>: a quarter less operand traffic per FLOP, 72 KB of LDS, never the default),
 // 128 x 64 tiles for N <= 1024 grids (59.3 -> 57.1 steps/s), 4-stage 128 x 128 x 32 (-10 % at K = 768),
 // 256 x 128 x 64 eight-wave tiles (lock-stepped waves idle the MFMA pipe at every barrier).
 
@@ -810,7 +805,7 @@ __device__ __forceinline__ void pp_lgkm0() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int PBM, bool AK, bool BK, bool H16, uint32_t EK, bool QSW = true>
+template <int PBM, bool AK, bool BK, bool H16, uint32_t EK>
 __global__ void __launch_bounds__(PP_NT, 1) gemm16_pp_kernel(const b2p_gemm_desc d, const EpiArgs ea, int tiles_m,
                                                             int tiles_n, int grp) {
   static_assert(PBM == 256 || (PBM == 192 && AK), "ping-pong tile rows: 256, or 192 with a k-contiguous A");
@@ -818,7 +813,7 @@ __global__ void __launch_bounds__(PP_NT, 1) gemm16_pp_kernel(const b2p_gemm_desc
   constexpr int HM = MI / 2;
   constexpr int PP_ABYTES = pp_abytes<PBM>(), PP_STAGE = pp_stage<PBM>();
   // quarter-scheduled DMA (256-row k-contiguous operands): see the K loop below
-  constexpr bool QS = QSW && PBM == 256 && AK && BK;
+  constexpr bool QS = PBM == 256 && AK && BK;
   // phase 3 reuses phase 0's B fragments (16 VGPRs) instead of reading them again; the runtime-kind
   // epilogue has no registers left for them
   constexpr bool KEEPB = EK != EK_RUNTIME;
@@ -1213,12 +1208,6 @@ void launch_small(const b2p_gemm_desc& d, const EpiArgs& ea, hipStream_t st, uns
 }
 template <bool AK, bool BK, bool H16, uint32_t EK>
 void launch_pp(const b2p_gemm_desc& d, const EpiArgs& ea, hipStream_t st, unsigned nwg, int tm, int tn, int grp) {
-  if constexpr (AK && BK) {
-    if (gemm16_variant_get() & 1) {
-      hipLaunchKernelGGL((gemm16_pp_kernel<256, AK, BK, H16, EK, false>), dim3(nwg), dim3(PP_NT), 0, st, d, ea, tm, tn, grp);
-      return;
-    }
-  }
   hipLaunchKernelGGL((gemm16_pp_kernel<256, AK, BK, H16, EK>), dim3(nwg), dim3(PP_NT), 0, st, d, ea, tm, tn, grp);
 }
 template <int PBM, bool H16, uint32_t EK>
@@ -1236,10 +1225,9 @@ void launch_pp192(const b2p_gemm_desc& d, const EpiArgs& ea, hipStream_t st, uns
 
 }  // namespace
 
-// kernel families of one instantiation unit: 0 = 128 x 128 (CfgSmall), 1 = 256 x 256 ping-pong,
-// 2 = 256 x 128 (CfgTall), 3 = 128 x 128 x 64 (CfgK64), 4 = 192 x 256 ping-pong (k-contiguous A),
-// 5 / 6 = 256 x 128 / 192 x 128 narrow ping-pong (both operands k-contiguous)
-enum { G16_SMALL = 0, G16_PP = 1, G16_TALL = 2, G16_K64 = 3, G16_PP192 = 4, G16_PN256 = 5, G16_PN192 = 6 };
+// kernel families of one instantiation unit: 128 x 128 (CfgSmall), 256 x 256 ping-pong, 192 x 256
+// ping-pong (k-contiguous A), 256 x 128 / 192 x 128 narrow ping-pong (both operands k-contiguous)
+enum { G16_SMALL, G16_PP, G16_PP192, G16_PN256, G16_PN192 };
 int gemm16_run_nt_bf16(const b2p_gemm_desc& d, hipStream_t st, int fam, uint32_t ek, unsigned nwg, int tm, int tn, int grp,
                        uint32_t* ctr);
 int gemm16_run_nt_f16(const b2p_gemm_desc& d, hipStream_t st, int fam, uint32_t ek, unsigned nwg, int tm, int tn, int grp,

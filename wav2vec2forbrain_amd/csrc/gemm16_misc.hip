@@ -9,9 +9,7 @@ int gemm16_run_other(const b2p_gemm_desc& d, hipStream_t st, int fam, uint32_t e
   const bool AK = d.A.inner_is_k != 0, BK = d.B.inner_is_k != 0;
   const bool h16 = d.A.dtype == 2;
   if (AK && BK) {   // bf16 with an implicit conv view on A
-    if (fam == G16_TALL) { if (ek == EK_GENERIC) launch_small<CfgTall, true, true, true, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp); else launch_small<CfgTall, true, true, true, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); }
-    else if (fam == G16_K64) { if (ek == EK_GENERIC) launch_small<CfgK64, true, true, true, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp); else launch_small<CfgK64, true, true, true, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); }
-    else { if (ek == EK_GENERIC) launch_small<CfgSmall, true, true, true, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp); else launch_small<CfgSmall, true, true, true, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); }
+    if (ek == EK_GENERIC) launch_small<CfgSmall, true, true, true, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp); else launch_small<CfgSmall, true, true, true, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp);
     return 0;
   }
   if (AK && h16) { if (ek == EK_GENERIC) launch_small<CfgSmall, true, false, false, true, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp); else launch_small<CfgSmall, true, false, false, true, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); return 0; }

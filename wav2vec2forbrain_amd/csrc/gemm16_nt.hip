@@ -31,15 +31,10 @@ int gemm16_run_nt_bf16(const b2p_gemm_desc& d, hipStream_t st, int fam, uint32_t
       default: if (w) launch_pn<256, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); else launch_pn<192, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); return 0;
     }
   }
-  if (fam == G16_SMALL) {
-    switch (ek) {
+  switch (ek) {   // G16_SMALL
 #define B2P_GO_(K) case K: launch_small<CfgSmall, true, true, false, false, K>(d, ea, st, nwg, tm, tn, grp); return 0;
-      B2P_KINDS_NT_BF16(B2P_GO_)
+    B2P_KINDS_NT_BF16(B2P_GO_)
 #undef B2P_GO_
-      default: if (ek == EK_GENERIC) launch_small<CfgSmall, true, true, false, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp); else launch_small<CfgSmall, true, true, false, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); return 0;
-    }
+    default: if (ek == EK_GENERIC) launch_small<CfgSmall, true, true, false, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp); else launch_small<CfgSmall, true, true, false, false, EK_RUNTIME>(d, ea, st, nwg, tm, tn, grp); return 0;
   }
-  if (fam == G16_TALL) launch_small<CfgTall, true, true, false, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp);
-  else launch_small<CfgK64, true, true, false, false, EK_GENERIC>(d, ea, st, nwg, tm, tn, grp);
-  return 0;
 }

@@ -184,36 +184,30 @@ def _prec_follow(cls):
 # when the (4-CU) GRU recurrence backward starts, so they fill the otherwise idle chip; they
 # accumulate into p.grad in the GEMM epilogue (beta = 1) instead of autograd's separate add.
 # join_wgrad() orders the side stream back into the main stream (train step, optimizer).
-_DIAG_SKIP_ACC = os.environ.get("B2P_DIAG_SKIP_SMALL_ACC") == "1"   # diagnostic only
-# diagnostic only (never a bench setting): drop the queued frozen weight-gradient launches, to measure how
-# much of the step's tail the side stream holds
-_DIAG_SKIP_WGRAD = os.environ.get("B2P_DIAG_SKIP_WGRAD") == "1"
+
 # workgroups a 128 x 128 split-K GEMM aims for (the split count is capped at one slice per 1024 of K)
-_SPLITK_WGS = int(os.environ.get("B2P_SPLITK_WGS", "512"))
-_PP_SPLIT = os.environ.get("B2P_PP_SPLIT", "0") == "1"   # every eligible split-K GEMM on the ping-pong kernel
+_SPLITK_WGS = 512
 # split-K GEMMs with at least this many outputs go to the 256 x 256 ping-pong kernel: the Conformer's
 # frozen weight gradients (4096 x 1024, 3072 x 1024; K = 7968 tokens) -8.6 ms per step; the base
 # model's (768 x 3072 and smaller) measured 0.2 ms slower on it, so they stay on the 128 x 128 split
-_PP_MIN_MN = int(os.environ.get("B2P_PP_MIN_MN", str(3 * 1024 * 1024)))
+_PP_MIN_MN = 3 * 1024 * 1024
 # ... and only while the unsplit 128 x 128 grid has fewer tiles than this (a grid that fills the chip by
 # itself needs no fp32 slabs and no reduce pass): the Conformer's 7968 x 1024 backward-data GEMMs (504
 # tiles) 69.73 -> 68.54 ms per step unsplit; the base model's 7968 x 768 (378 tiles, 1.5 rounds of the
 # CUs) stay split (14.99 vs 15.13 ms unsplit), profiles/r05o_pp_split_rule_ab.txt
-_PP_SPLIT_MAX_BLOCKS = int(os.environ.get("B2P_PP_SPLIT_MAX_BLOCKS", "448"))
+_PP_SPLIT_MAX_BLOCKS = 448
 # ... unless K is long enough that one 128 x 128 tile's K loop dominates (the front end's implicit-unfold
 # backward-data GEMM, 8192 x 1024 x 24576 in the Conformer step: 1.39 ms unsplit on 128 x 128 tiles)
-_PP_SPLIT_LONG_K = int(os.environ.get("B2P_PP_SPLIT_LONG_K", "8192"))
+_PP_SPLIT_LONG_K = 8192
 
 
 class _Deferred:
     ids: set = set()
-    queue: list = []          # (fn, tensors used, key = id of the parameter it updates)
+    queue: list = []          # (fn, tensors used, _WSpec or None)
     accs: list = []           # (parameter, small gradient) pairs accumulated in one launch
-    sides: list = []          # side streams (B2P_SIDE_STREAMS, default 1: several concurrent weight-
-                              # gradient streams starved the main stream, 15.1 -> 17.2-18.8 ms/step)
-    lane: dict = {}           # parameter id -> side stream index (fixed: one stream per parameter)
+    side = None               # the side stream (one: several concurrent weight-gradient streams starved
+                              # the main stream, 15.1 -> 17.2-18.8 ms/step)
     pending = False
-    split = os.environ.get("B2P_DEFER_SPLIT", "1") == "1"   # split-K for the deferred GEMMs
 
 
 def set_deferred_wgrad(params, names=None) -> None:
@@ -236,7 +230,7 @@ def set_deferred_wgrad(params, names=None) -> None:
 
 
 def deferred_wgrad_active() -> bool:
-    """Some parameter's gradient work is deferred to the side streams (set_deferred_wgrad)."""
+    """Some parameter's gradient work is deferred to the side stream (set_deferred_wgrad)."""
     return bool(_Deferred.ids)
 
 
@@ -254,10 +248,6 @@ def _acc_param(p, g) -> None:
 def _defer_acc(p, g) -> None:
     """Accumulate a ready gradient tensor into p.grad on the side stream (all of a flush's small
     accumulations go out as ONE multi-tensor launch, b2p_accum_recs)."""
-    if _DIAG_SKIP_ACC:
-        return
-    if not _LAZY_COLSUM:
-        g = _mat(g)
     _Deferred.accs.append((p, g))
 
 
@@ -374,14 +364,14 @@ def _defer_wgemm_rows(ps, fn, *tensors) -> None:
                     r += n
         finally:
             _state.prec = old
-    _Deferred.queue.append((_gate_wrap(run), tensors, id(ps[0]), None))
+    _Deferred.queue.append((_gate_wrap(run), tensors, None))
 
 
 def _defer_bias_rows(ps, x, M, N) -> bool:
     """The column sums of x (M x N fp32, N = the concatenated lengths of the bias vectors ps) as the
     gradients of frozen biases: queued for the side stream (the same b2p_colsum launch, accumulating into
     their .grad) instead of run on the main stream. False when a bias is not a deferred frozen one."""
-    if not (_LAZY_COLSUM and all(_defer_ok(q) for q in ps)):
+    if not all(_defer_ok(q) for q in ps):
         return False
     _defer_wgemm_rows(ps, lambda out, beta: colsum(x, M, N, out, accumulate=beta == 1.0), x)
     return True
@@ -396,7 +386,7 @@ def _defer_dwconv_wgrad(w, u, dc, B, T, D, K) -> None:
         g = torch.empty_like(w)
         _lib.call("b2p_dwconv_bwd", _p(u), _p(w), _p(dc), None, _p(g), B, T, D, K, _p(ws), _st())
         _defer_acc(w, g)
-    _Deferred.queue.append((_gate_wrap(run), (u, dc), id(w), None))
+    _Deferred.queue.append((_gate_wrap(run), (u, dc), None))
 
 
 def _defer_wgemm(p, fn, *tensors) -> None:
@@ -414,7 +404,7 @@ def _defer_wgemm(p, fn, *tensors) -> None:
                 fn(p.grad, 1.0)
         finally:
             _state.prec = old
-    _Deferred.queue.append((_gate_wrap(run), tensors, id(p), None))
+    _Deferred.queue.append((_gate_wrap(run), tensors, None))
 
 
 class _WSpec:
@@ -428,23 +418,19 @@ class _WSpec:
         self.gate, self.prec = _state.gate, _prec()
 
     def key(self):
-        # parameters by (rows, numel), not shape: a Conformer's out-projection weight (D, D) and its
-        # pointwise conv-2 weight (D, D, 1) share one batched launch (two 1.5-round grids -> one of 3)
         return (self.M, self.N, self.K, self.lda, self.ldb, self.a.dtype, self.b.dtype, self.prec,
                 tuple(_pkey(p) for p in self.ps))
 
 
-# B2P_WGRAD_MERGE=1: batch groups keyed by (rows, numel) per parameter instead of the full shapes (measured
-# neutral on Conformer-large: 64.93 / 65.12 vs 65.14 / 65.06 ms, profiles/r05aw_wgrad_merge_ab.txt)
-_WGRAD_MERGE = os.environ.get("B2P_WGRAD_MERGE", "0") == "1"
-
-
+# batch groups are keyed by the parameters' full shapes; keyed by (rows, numel), so that the Conformer's
+# out-projection (D, D) and pointwise conv-2 (D, D, 1) weights share a launch, measured neutral on
+# Conformer-large: 64.93 / 65.12 vs 65.14 / 65.06 ms, profiles/r05aw_wgrad_merge_ab.txt
 def _pkey(p):
-    return (p.shape[0], p.numel()) if _WGRAD_MERGE else tuple(p.shape)
+    return tuple(p.shape)
 
 
-# B2P_WGRAD_BATCH=0: every deferred frozen weight gradient is its own (split-K) launch
-_WGRAD_BATCH = [os.environ.get("B2P_WGRAD_BATCH", "1") != "0"]
+# False (tests): every deferred frozen weight gradient is its own (split-K) launch
+_WGRAD_BATCH = [True]
 
 
 def _defer_wspec(ps, M, N, K, a, a_off, lda, b, ldb) -> None:
@@ -457,8 +443,8 @@ def _defer_wspec(ps, M, N, K, a, a_off, lda, b, ldb) -> None:
         _defer_wgemm(ps[0], fn, a, b)
     else:
         _defer_wgemm_rows(ps, fn, a, b)
-    fn_, ts, key, _ = _Deferred.queue[-1]
-    _Deferred.queue[-1] = (fn_, ts, key, spec)
+    fn_, ts, _ = _Deferred.queue[-1]
+    _Deferred.queue[-1] = (fn_, ts, spec)
 
 
 def _i64_dev(vals, dev):
@@ -486,15 +472,6 @@ def _gathered_op(ts, offs, ld, dtype):
     o.conv = 0
     o.dtype = 1 if dtype == BF16 else 2
     return o, idx
-
-
-_WGRAD_DEBUG = os.environ.get("B2P_WGRAD_DEBUG") == "1"
-
-
-def _wdbg(msg, specs):
-    if _WGRAD_DEBUG:
-        s0 = specs[0]
-        print(f"wgrad batch {s0.M}x{s0.N}x{s0.K} x{len(specs)}: {msg}", flush=True)
 
 
 class _Home:
@@ -597,7 +574,6 @@ def _run_wspecs(specs) -> bool:
     cap = capturing()
     if home is None:
         if cap:   # a home is allocated (zeroed) outside captures only
-            _wdbg("no home before the capture", specs)
             return False
         # slots: one per layer holding a role that leads a slot of this shape (the roles of the specs'
         # first parameters; the Conformer's ffn1 / ffn2 share a home, Wq / Wk / Wv / Wo share a shape but
@@ -618,7 +594,6 @@ def _run_wspecs(specs) -> bool:
     for sp in specs:
         i = home.ensure(sp.ps)
         if i is None or (cap and not home.bindable(i, sp.ps)):
-            _wdbg("slot unavailable", specs)
             return False
         at[i] = sp
     for i, sp in at.items():
@@ -638,8 +613,7 @@ def _run_wspecs(specs) -> bool:
         fill = next(m for m in mem if m is not None)
         A, ia = _gathered_op([(m or fill).a for m in mem], [(m or fill).a_off for m in mem], s0.lda, s0.a.dtype)
         B, ib = _gathered_op([(m or fill).b for m in mem], [0] * len(mem), s0.ldb, s0.b.dtype)
-        if A is None or B is None:
-            _wdbg("operands not 16-byte aligned", specs)
+        if A is None or B is None:   # operands not 16-byte aligned
             return False
         chunks.append((c0, c1, mem, A, ia, B, ib))
     old_prec, old_split = _state.prec, _state.nosplit
@@ -662,46 +636,40 @@ def _run_wspecs(specs) -> bool:
                     if gp is not None:
                         _lib.call("b2p_set_gate_batch", None)
             del gp
-            _wdbg(f"batched slots {c0}..{c1} ({sum(m is not None for m in mem)} present)", specs)
         del chunks
     finally:
         _state.prec, _state.nosplit = old_prec, old_split
     return True
 
 
+def _side_stream(main):
+    """The stream the deferred work runs on: the side stream, made on first use (the main stream itself
+    under SERIAL_SIDE)."""
+    if _Deferred.side is None:
+        _Deferred.side = torch.cuda.Stream(device=main.device)
+    return main if SERIAL_SIDE else _Deferred.side
+
+
 def flush_wgrad(after=None) -> None:
-    """Launch the queued frozen-parameter gradient work on the side streams, ordered after the event
+    """Launch the queued frozen-parameter gradient work on the side stream, ordered after the event
     `after` (recorded by the caller before a long kernel it wants to run beside) or after everything
-    the main stream has queued so far. Each parameter's work always goes to the same side stream
-    (its accumulations stay ordered); independent weight-gradient GEMMs on different streams run
-    concurrently, which fills the chip without split-K partial sums and their reduce launches."""
-    if _WGRAD_DEBUG:
-        print(f"flush_wgrad: {len(_Deferred.queue)} queued, {len(_Deferred.accs)} accs, after={after is not None}, "
-              f"capturing={capturing()}", flush=True)
-    if _DIAG_SKIP_WGRAD:
-        _Deferred.queue.clear()
+    the main stream has queued so far. One stream keeps every parameter's accumulations ordered."""
     if not _Deferred.queue and not _Deferred.accs:
         return
     main = torch.cuda.current_stream()
-    if not _Deferred.sides:
-        n = max(1, int(os.environ.get("B2P_SIDE_STREAMS", "1")))
-        _Deferred.sides = [torch.cuda.Stream(device=main.device) for _ in range(n)]
-    sides = [main] if SERIAL_SIDE else _Deferred.sides
-    for sd in sides:
-        if after is not None:
-            sd.wait_event(after)
-        else:
-            sd.wait_stream(main)
+    sd = _side_stream(main)
+    if after is not None:
+        sd.wait_event(after)
+    else:
+        sd.wait_stream(main)
     old = _state.nosplit
-    _state.nosplit = not _Deferred.split
+    _state.nosplit = False   # split-K for the deferred GEMMs
     try:
-        # same-shape frozen weight gradients of the layers: one batched launch per shape (one side
-        # stream keeps every parameter's work on one stream, as the lanes below do)
-        batch = _WGRAD_BATCH[0] and len(sides) == 1
+        # same-shape frozen weight gradients of the layers: one batched launch per shape
         groups, order = {}, []
         for ent in _Deferred.queue:
-            spec = ent[3]
-            if batch and spec is not None:
+            spec = ent[2]
+            if _WGRAD_BATCH[0] and spec is not None:
                 k = spec.key()
                 if k not in groups:
                     groups[k] = []
@@ -711,20 +679,18 @@ def flush_wgrad(after=None) -> None:
                 order.append(("s", ent))
         for kind, x in order:
             ents = groups[x] if kind == "g" else [x]
-            sd = sides[_Deferred.lane.setdefault(ents[0][2], len(_Deferred.lane) % len(sides))]
             with torch.cuda.stream(sd):
-                batched = kind == "g" and _run_wspecs([e[3] for e in ents])
+                batched = kind == "g" and _run_wspecs([e[2] for e in ents])
                 if kind == "g" and not batched:
                     WGRAD_FALLBACKS[0] += 1
                 if not batched:
-                    for fn, _, key, _ in ents:
-                        with torch.cuda.stream(sides[_Deferred.lane.setdefault(key, len(_Deferred.lane) % len(sides))]):
-                            fn()
-            for _, ts, key, _ in ents:
+                    for fn, _, _ in ents:
+                        fn()
+            for _, ts, _ in ents:
                 for t in ts:
-                    t.record_stream(sd if kind == "g" else sides[_Deferred.lane[key]])
+                    t.record_stream(sd)
         if _Deferred.accs:
-            _flush_accs(sides[0])
+            _flush_accs(sd)
     finally:
         _state.nosplit = old
     _Deferred.queue.clear()
@@ -738,16 +704,14 @@ SERIAL_SIDE = os.environ.get("B2P_SERIAL_SIDE", "0") == "1"
 
 
 def _join_sides() -> None:
-    """The current stream waits for the work already flushed to the side streams (the queue stays)."""
+    """The current stream waits for the work already flushed to the side stream (the queue stays)."""
     if _Deferred.pending:
-        cur = torch.cuda.current_stream()
-        for sd in _Deferred.sides:
-            cur.wait_stream(sd)
+        torch.cuda.current_stream().wait_stream(_Deferred.side)
         _Deferred.pending = False
 
 
 def join_wgrad() -> None:
-    """Flush, then make the current stream wait for the side streams."""
+    """Flush, then make the current stream wait for the side stream."""
     flush_wgrad()
     _join_sides()
 
@@ -943,7 +907,7 @@ def gemm(M, N, K, A: Operand, B: Operand, C, ldc, c_off=0, cbs1=0, cbs2=0, nz1=1
         ks = 1
         tpp = -(-M // 256) * -(-N // 256) * nz1 * nz2
         kpp = min(-(-160 // tpp), K // 1024)
-        if (b16 and (_PP_SPLIT or M * N * nz1 * nz2 >= _PP_MIN_MN) and tpp * kpp >= 160 and kpp >= 2
+        if (b16 and M * N * nz1 * nz2 >= _PP_MIN_MN and tpp * kpp >= 160 and kpp >= 2
                 and (blocks < _PP_SPLIT_MAX_BLOCKS or K >= _PP_SPLIT_LONG_K)):
             # 256x256 ping-pong tiles (gemm16.hip) over >= 1024-deep K slices, ~160-200 workgroups
             # (the frozen weight gradients, K = tokens): fewer, larger tiles than the 128 x 128 split
@@ -991,11 +955,11 @@ def _x3_role(A, B) -> str:
 
 
 def _x3_form(A, B) -> str:
-    """How the bf16x3 mode runs this GEMM (B2P_X3_SINGLE / the Trainer policy's role set, or the
+    """How the bf16x3 mode runs this GEMM (x3_forms: the Trainer policy's role set, or the
     diagnostic switches of tools/traj_err_ft.py): '' split-bf16 three-term images; '1' single pass as in
     the bf16 mode (forward on fp16 operands); '2a' / '2b' two-term images (hi*hi + lo*hi: A kept to
     ~16 bits, B rounded to bf16 / the reverse)."""
-    forms = _state.x3forms if _state.x3forms is not None else _X3_SINGLE
+    forms = _state.x3forms or ()
     if not forms and not DIAG_SWITCHES:
         return ""
     role = _x3_role(A, B)
@@ -1008,8 +972,6 @@ def _x3_form(A, B) -> str:
 def _x3_single(A, B) -> bool:
     return _x3_form(A, B) == "1"
 
-
-_X3_SINGLE = set(filter(None, os.environ.get("B2P_X3_SINGLE", "").split(",")))
 
 # The Trainer's bf16x3 policy (configs[4]: the w2v encoder trained) runs the weight-gradient GEMMs
 # single-pass (bf16) and the backward-data GEMMs on two-term images (the gradient rounded to bf16, the
@@ -1034,7 +996,7 @@ def x3_mfma_work(forms) -> float:
 
 @contextlib.contextmanager
 def x3_forms(forms):
-    """The bf16x3 mode's per-role GEMM forms inside (see _x3_form; None: B2P_X3_SINGLE)."""
+    """The bf16x3 mode's per-role GEMM forms inside (see _x3_form; None: three-term everywhere)."""
     old = _state.x3forms
     _state.x3forms = None if forms is None else frozenset(forms)
     try:
@@ -1044,8 +1006,8 @@ def x3_forms(forms):
 
 
 # bf16x3 mode: large plain fp32-operand GEMMs run as one bf16 GEMM over split-bf16 operand images
-# (B2P_X3_SPLIT=0: the fp32-operand kernel's three-MFMA form, csrc/gemm.hip precision 3)
-_X3_SPLIT = [os.environ.get("B2P_X3_SPLIT", "1") != "0"]
+# (False, tests: the fp32-operand kernel's three-MFMA form, csrc/gemm.hip precision 3)
+_X3_SPLIT = [True]
 
 
 _SPLIT2 = 0x10   # b2p_split3_bf16 pattern flag: two K-blocks instead of three
@@ -1079,8 +1041,8 @@ _SPLITK_CTR = [True]
 GEMM_LOG = None
 
 # fp32-operand GEMMs at least this large (2*M*N*K) are run on staged 16-bit operand copies
-_AUTO16 = os.environ.get("B2P_GEMM_AUTO16", "1") == "1"
-_AUTO16_MIN_FLOP = float(os.environ.get("B2P_GEMM_AUTO16_MIN_GFLOP", "2")) * 1e9
+_AUTO16 = True   # False (tests): the fp32-operand kernel whatever the size
+_AUTO16_MIN_FLOP = 2e9
 
 
 def _auto16_ok(M, N, K, A, B, nz1, nz2) -> bool:
@@ -1192,11 +1154,6 @@ def _mat(g):
     return g.materialize() if isinstance(g, ColsumParts) else g
 
 
-# B2P_LAZY_COLSUM=0 (A/B): deferred bias gradients are finished by a colsum_p2 launch on the main
-# stream, as before, instead of inside the side stream's batched accumulation
-_LAZY_COLSUM = os.environ.get("B2P_LAZY_COLSUM", "1") != "0"
-
-
 def colsum(x2d_ptr_tensor, M, N, out, ld=None, accumulate=False):
     ws = _colsum_ws(M, N, out.device)
     _lib.call("b2p_colsum", _p(x2d_ptr_tensor), M, N, ld or N, _p(out), int(accumulate), _p(ws), _st())
@@ -1231,14 +1188,13 @@ def _ln_fwd(x2d, g, b, eps, drop_p=0.0, seed=0):
 
 
 _LN_BWD_ROWS = 16   # rows per block of ln_bwd_k (csrc/elementwise.hip LN_BWD_ROWS): the partials' row count
-_LN_LAZY = os.environ.get("B2P_LN_LAZY", "1") != "0"   # B2P_LN_LAZY=0: reduce them on the main stream (A/B)
 
 
 def _ln_lazy(lazy, need_params, dbias_in) -> bool:
     """The LayerNorm backward leaves its parameter gradients as block partials (ColsumParts, finished in
     the side stream's batched accumulation) when every parameter they belong to is a deferred frozen
     one: lazy = (gamma, beta, the dropout-input bias or None), matching dbias_in."""
-    return (_LAZY_COLSUM and _LN_LAZY and lazy is not None and need_params and (dbias_in is None) == (lazy[2] is None)
+    return (lazy is not None and need_params and (dbias_in is None) == (lazy[2] is None)
             and all(_defer_ok(q) for q in lazy if q is not None))
 
 
@@ -1549,14 +1505,11 @@ class Unfolded:
         return win.permute(0, 1, 3, 2).reshape(B, self.T, C * self.kernel)
 
 
-# bf16 mode's GRU layer 0 reads the Unfold through an implicit overlapping-row view (B2P_UNFOLD_IMPLICIT=0:
-# the materialised bf16 unfold + col2im of round 3, for A/B checks)
-_UNFOLD_IMPLICIT = [os.environ.get("B2P_UNFOLD_IMPLICIT", "1") != "0"]
-# persistent MFMA recurrence in bf16 mode (B2P_GRU16=0 selects the per-step fp32 kernels, for A/B checks)
-_GRU16 = [os.environ.get("B2P_GRU16", "1") != "0"]
+# persistent MFMA recurrence in bf16 mode (False selects the per-step fp32 kernels, for A/B checks)
+_GRU16 = [True]
 # hidden sizes one CU cannot hold (Conformer H = 512): the multi-CU persistent kernels (csrc/grumc.hip)
-# in bf16 mode (B2P_GRUMC=0: per-step kernels, for A/B checks)
-_GRUMC = [os.environ.get("B2P_GRUMC", "1") != "0"]
+# in bf16 mode (False: per-step kernels, for A/B checks; tools/traj_err.py)
+_GRUMC = [True]
 # diagnostic (tools/traj_err.py): None = the backward follows the forward's choice; True / False force
 # the multi-CU / per-step fp32 backward recurrence (same saved layout)
 _GRUMC_BWD = [None]
@@ -1663,8 +1616,7 @@ class _GRULayer(torch.autograd.Function):
         # into the input projection bias
         # the bf16x3 mode's 'grurec1' form (X3_POLICY_FORMS): the persistent recurrences (fp16 / bf16 MFMA on
         # W_hh h) with the input-projection and weight-gradient GEMMs kept in the mode's split-bf16 form
-        fast = bf16_mode() or (_state.prec == 3 and "grurec1" in (_state.x3forms if _state.x3forms is not None
-                                                                     else _X3_SINGLE))
+        fast = bf16_mode() or (_state.prec == 3 and "grurec1" in (_state.x3forms or ()))
         use16 = fast and _GRU16[0] and bool(_lib.load().b2p_gru16_supported(H))
         usemc = fast and not use16 and _GRUMC[0] and bool(_lib.load().b2p_gru_mc_supported(H))
         # the step's stacked recurrent weights / biases and the concatenated input-projection bias (with
@@ -1684,8 +1636,8 @@ class _GRULayer(torch.autograd.Function):
                          _p(bias_cat, d * G3 + 2 * H), _p(bih[d], 2 * H) or 0, 0, H]
         arr = (ctypes.c_int64 * len(recs))(*recs)
         _lib.call("b2p_gather_recs", arr, len(recs) // 4, _st())
-        implicit = (unf_meta is not None and bf16_mode() and L % stride == 0 and ktaps % stride == 0 and C % 4 == 0
-                    and _UNFOLD_IMPLICIT[0])
+        # bf16 mode's layer 0 reads the Unfold through an implicit overlapping-row view
+        implicit = unf_meta is not None and bf16_mode() and L % stride == 0 and ktaps % stride == 0 and C % 4 == 0
         if implicit:
             # implicit Unfold (csrc/elementwise.hip "implicit Unfold operands"): the GEMM reads a 16-bit copy
             # of x through an overlapping-row view (row stride stride*C); fp16 operands under forward_f16
@@ -1907,8 +1859,7 @@ def gru_layer(x, H, ndir, weights, h0=None):
     bf16 mode (persistent MFMA recurrences, fp16 forward operands) and its backward follows it
     (_prec_follow: block 'gru'), instead of the fp32 operators' per-time-step recurrence kernels."""
     with _fp32_if("gru"):
-        forms = _state.x3forms if _state.x3forms is not None else _X3_SINGLE
-        ctxm = precision("bf16") if (_state.prec == 3 and "gru1" in forms) else contextlib.nullcontext()
+        ctxm = precision("bf16") if (_state.prec == 3 and "gru1" in (_state.x3forms or ())) else contextlib.nullcontext()
         with ctxm:
             if isinstance(x, Unfolded):
                 return _GRULayer.apply(x.src, (x.kernel, x.stride), H, ndir, h0, *weights)
@@ -1918,9 +1869,6 @@ def gru_layer(x, H, ndir, weights, h0=None):
 # =====================================================================================
 # Linear / dropout
 # =====================================================================================
-_LINEAR_DEFER = os.environ.get("B2P_LINEAR_WGRAD_DEFER", "0") == "1"   # 1: frozen Linear dW on the side stream (measured neutral: base 14.03 either way, Conformer 64.79 / 64.80 ms)
-
-
 @_prec_follow
 class _Linear(torch.autograd.Function):
     @staticmethod
@@ -1949,13 +1897,10 @@ class _Linear(torch.autograd.Function):
             dx = torch.empty_like(x)
             mm_nn(dy, W, dx)
         if ctx.needs_input_grad[1]:
-            if _LAZY_COLSUM and _LINEAR_DEFER and _defer_ok(ctx.prm[0]):
-                # frozen weight (lm_head in configs 1-3): the weight-gradient GEMM itself on the side stream,
-                # accumulating into .grad (it ran on 6 workgroups for ~47 us on the main stream)
-                _defer_wgemm(ctx.prm[0], lambda out, beta, dy=dy, x=x: mm_tn(dy, x, out, beta=beta), dy, x)
-            else:
-                dW = torch.empty_like(W)
-                mm_tn(dy, x, dW)
+            # a frozen weight's (lm_head in configs 1-3) gradient GEMM stays here: queued for the side stream
+            # it measured neutral (base 14.03 ms either way, Conformer 64.79 / 64.80 ms)
+            dW = torch.empty_like(W)
+            mm_tn(dy, x, dW)
         if ctx.has_b and ctx.needs_input_grad[2] and not _defer_bias_rows((ctx.prm[1],), dy, dy.numel() // N, N):
             db = torch.empty(N, device=x.device)
             colsum(dy, dy.numel() // N, N, db)
@@ -2011,8 +1956,8 @@ class _SkipSlot:
 
 
 _SKIP_CLAIM: dict = {}   # data_ptr of a layer input -> its _SkipSlot, while that layer's forward runs
-# B2P_LD_SKIP_FOLD=0: the skip gradient goes back through autograd (its own add kernel), as before
-_LD_SKIP_FOLD = os.environ.get("B2P_LD_SKIP_FOLD", "1") != "0"
+# False (tests): the skip gradient goes back through autograd (its own add kernel), as before
+_LD_SKIP_FOLD = True
 
 
 def _skip_claim(x):
@@ -2047,8 +1992,8 @@ class _LayerDropSelect(torch.autograd.Function):
         b16 = bf16_mode()
         x16, y16 = (_b16_of(x), _b16_of(y)) if b16 else (None, None)
         # the fp16 copy too when the layer made one (post-LN forward_f16): the next layer reads it uncast
-        yh = _h16_of(y) if b16 and _LD_SELECT_H else None
-        if _LD_INPLACE and (not b16 or y16 is not None):
+        yh = _h16_of(y) if b16 else None
+        if not b16 or y16 is not None:
             # in place: the output is a fresh tensor over y's storage (and y's 16-bit copies), overwritten
             # by x only when the replay's draw skips the layer, so a kept layer's select moves no bytes.
             # Nothing reads y's old values after a skip: the layer's own backward is gated off then.
@@ -2080,11 +2025,7 @@ class _LayerDropSelect(torch.autograd.Function):
         return d_skip, d_keep, None, None, None
 
 
-_LD_SELECT_H = os.environ.get("B2P_LD_SELECT_H", "1") != "0"   # 0: no fp16 copy from the select (A/B)
-_LD_INPLACE = os.environ.get("B2P_LD_INPLACE", "1") != "0"     # 0: the select writes a new tensor (A/B)
 LAYERDROP_LOG = None   # tests: when a list, layerdrop_layer appends each layer's draw seed
-# diagnostic only (B2P_GRAPH_LAYERDROP=0): a captured step keeps the host draw made at capture time
-GRAPH_LAYERDROP = os.environ.get("B2P_GRAPH_LAYERDROP", "1") != "0"
 
 
 def capturing() -> bool:
@@ -2092,8 +2033,6 @@ def capturing() -> bool:
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
-# B2P_LAYERDROP_GATE=0: a skipped layer still computes (diagnostic / A-B of the gate)
-LAYERDROP_GATE = os.environ.get("B2P_LAYERDROP_GATE", "1") != "0"
 _GATE_FLAGS: list = []
 # parameter id -> (weak reference, the device gate of its layer in the most recently captured step).
 # HipAdam reads it while capturing: a parameter of a layer this replay dropped is left untouched, as
@@ -2115,12 +2054,11 @@ def layerdrop_layer(layer, x, p):
     if LAYERDROP_LOG is not None:
         LAYERDROP_LOG.append(seed)
     bufs = [b for b in layer.buffers() if b.is_floating_point() and b.numel() % 4 == 0]
-    if LAYERDROP_GATE:
-        # BatchNorm running statistics are updated by bn_finalize_k, which reads the gate itself and
-        # leaves them untouched in a replay that skips the layer: no snapshot / restore launches
-        bn = {id(t) for m in layer.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
-              for t in (m.running_mean, m.running_var) if t is not None}
-        bufs = [b for b in bufs if id(b) not in bn]
+    # BatchNorm running statistics are updated by bn_finalize_k, which reads the gate itself and
+    # leaves them untouched in a replay that skips the layer: no snapshot / restore launches
+    bn = {id(t) for m in layer.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)
+          for t in (m.running_mean, m.running_var) if t is not None}
+    bufs = [b for b in bufs if id(b) not in bn]
     olds = [b.clone() for b in bufs]
     y = None
     flag = torch.empty(1, dtype=torch.int32, device=x.device)
@@ -2129,16 +2067,13 @@ def layerdrop_layer(layer, x, p):
     for prm in layer.parameters():
         _LD_PARAM_GATE[id(prm)] = (weakref.ref(prm), flag)
     slot = None
-    if _LD_SKIP_FOLD and LAYERDROP_GATE and x.requires_grad and x.is_contiguous():
+    if _LD_SKIP_FOLD and x.requires_grad and x.is_contiguous():
         slot = _SkipSlot()
         _SKIP_CLAIM[x.data_ptr()] = slot
     try:
-        if LAYERDROP_GATE:
-            # the layer's GEMMs and fused attention (forward, backward, deferred weight gradients) read
-            # this replay's draw and do no work when it skips the layer; the select below still routes
-            with _gated(flag):
-                y = layer(x)
-        else:
+        # the layer's GEMMs and fused attention (forward, backward, deferred weight gradients) read
+        # this replay's draw and do no work when it skips the layer; the select below still routes
+        with _gated(flag):
             y = layer(x)
     finally:
         if slot is not None:
@@ -2273,14 +2208,14 @@ def _posconv16_bwd(ctx, e16, wg, wv, w, norms, pre, dxsum, dlg, dlb):
         _lib.call("b2p_weight_norm_bwd", _p(wg), _p(wv), _p(norms), _p(dw), _p(g_), _p(v_), O, Ig, K, _p(ws), _st())
         return g_, v_
 
-    if ng[1] and ng[2] and _LAZY_COLSUM and _defer_ok(ctx.prm[0]) and _defer_ok(ctx.prm[1]):
+    if ng[1] and ng[2] and _defer_ok(ctx.prm[0]) and _defer_ok(ctx.prm[1]):
         # frozen weight-normed pos-conv: its weight gradient (conv wgrad, permute, weight-norm backward)
         # runs on the side stream and joins the flush's batched accumulation
         def run():
             g_, v_ = wgrad()
             _defer_acc(ctx.prm[0], g_)
             _defer_acc(ctx.prm[1], v_)
-        _Deferred.queue.append((_gate_wrap(run), (dpre16, e16, norms), id(ctx.prm[0]), None))
+        _Deferred.queue.append((_gate_wrap(run), (dpre16, e16, norms), None))
     elif ng[1] or ng[2]:
         dg, dv = wgrad()
     # frozen parameters' gradients join the batched side-stream accumulation (no autograd adds)
@@ -2363,8 +2298,7 @@ def attn16_ok(T, dh) -> bool:
 # backward reads the same block as before. Layers take the blocks in call order (a host-skipped
 # LayerDrop layer leaves one unused: every block is an independent draw). Measured: attention forward
 # 38.4 -> 33.2 us per base layer, the step unchanged within noise (profiles/r05ag_attn_keep_ahead_ab.txt).
-# B2P_ATTN_KEEP_AHEAD=0: each forward hashes its own (A/B).
-_KEEP_AHEAD = [os.environ.get("B2P_ATTN_KEEP_AHEAD", "1") != "0"]
+# Without a plan (eval, longer windows, other modes) each forward hashes its own.
 _KEEP_PLAN: list = [None]
 
 
@@ -2382,10 +2316,7 @@ class _KeepPlan:
         if self.ev is not None:
             return
         main = torch.cuda.current_stream()
-        if not _Deferred.sides:
-            n_side = max(1, int(os.environ.get("B2P_SIDE_STREAMS", "1")))
-            _Deferred.sides = [torch.cuda.Stream(device=main.device) for _ in range(n_side)]
-        side = main if SERIAL_SIDE else _Deferred.sides[0]
+        side = _side_stream(main)
         B, T, nh, p = self.key
         side.wait_stream(main)
         with torch.cuda.stream(side):
@@ -2413,7 +2344,7 @@ class _KeepPlan:
 def attn_keep_plan(n_layers, B, T, nh, dh, p_attn, training):
     """Around a model forward: draw the encoder's attention keep masks ahead (see _KeepPlan) when the
     fused 16-bit attention with a stored mask will run (bf16 mode, training, p > 0, T' <= 256)."""
-    on = (_KEEP_AHEAD[0] and training and p_attn > 0 and n_layers > 0 and bf16_mode()
+    on = (training and p_attn > 0 and n_layers > 0 and bf16_mode()
           and attn16_ok(T, dh) and T <= 256 and _KEEP_PLAN[0] is None)
     if not on:
         yield
@@ -2439,38 +2370,16 @@ def attn_keep_plan_cfg(cfg, brain_encoder, inputs, training):
                           cfg.hidden_size // cfg.num_attention_heads, cfg.attention_dropout, training)
 
 
-# Where the queued frozen weight gradients go out relative to the GRU recurrence backward (A/B):
-# "after" = flushed after the recurrence launch, ordered after the event before it; "first" = flushed
-# before the recurrence launch; "fork" = the recurrence itself launched on a stream of its own (forked
-# from and joined back into the current stream), the flush after it. All three measured equal step
-# times (base 14.49 / 14.49 / 14.47 ms, Conformer 66.11 / - / 65.96 ms: profiles/r05ak_gru_bwd_mode_ab.txt).
-_GRU_BWD_MODE = os.environ.get("B2P_GRU_BWD_MODE", "after")
-_GRU_STREAM: list = [None]
-
-
 def _gru_bwd_launch(launch) -> None:
     """Launch a GRU recurrence backward (launch() on the current stream) with the frozen weight
-    gradients flushed beside it (flush_wgrad), in the order _GRU_BWD_MODE selects."""
+    gradients flushed beside it (flush_wgrad): after the recurrence launch, ordered after the event
+    before it. Flushed before the launch, or with the recurrence on a stream of its own, the step times
+    measured equal (base 14.49 / 14.49 / 14.47 ms, Conformer 66.11 / - / 65.96 ms:
+    profiles/r05ak_gru_bwd_mode_ab.txt)."""
     ev = torch.cuda.Event()
     ev.record()
-    if _GRU_BWD_MODE == "first":
-        flush_wgrad(ev)
-        launch()
-    elif _GRU_BWD_MODE == "fork":
-        main = torch.cuda.current_stream()
-        if _GRU_STREAM[0] is None:
-            _GRU_STREAM[0] = torch.cuda.Stream(device=main.device)
-        gs = _GRU_STREAM[0]
-        gs.wait_event(ev)
-        with torch.cuda.stream(gs):
-            launch()
-            done = torch.cuda.Event()
-            done.record()
-        flush_wgrad(ev)
-        main.wait_event(done)
-    else:
-        launch()
-        flush_wgrad(ev)
+    launch()
+    flush_wgrad(ev)
 
 
 def _keep_take(B, T, nh, p_attn):
@@ -2500,8 +2409,7 @@ def _attn16_fwd(qkv16, B, T, nh, dh, p_attn, seed, want_mask=False):
 # (csrc/attn16.hip b2p_attn16_fwd_f16). bf16's 8-bit mantissa on the scores / probabilities biased the
 # 24-layer models' CTC loss by ~1e-3 relative (tools/fixture_err.py: with the attention alone in exact
 # fp32 the Conformer-large error fell from 1.0e-3 to 8e-5). The QKV projection writes the fp16 operand,
-# the backward recomputes the scores from it (b2p_attn16_bwd_f16); B2P_ATTN_F16=0 keeps bf16 (A/B).
-ATTN_F16 = os.environ.get("B2P_ATTN_F16", "1") != "0"
+# the backward recomputes the scores from it (b2p_attn16_bwd_f16).
 
 
 def _attn16_fwd_f16(qkvh, B, T, nh, dh, p_attn, seed):
@@ -2661,22 +2569,18 @@ class _EncoderLayer16(torch.autograd.Function):
         x16 = to16(x).view(NT, D)
         bqkv = bias_cat(bq, bk, bv) if any(b is not None for b in (bq, bk, bv)) else None
         fused = attn16_ok(T, dh)
-        if fused and ATTN_F16 and _state.fwd16:
+        if fused and _state.fwd16:
             return _EncoderLayer16._forward_f16(ctx, x, x16, cfg, bqkv, B, T, D, nh, dh, wq, bq, wk, bk, wv, bv, wo,
                                                 bo, g1, be1, w1, b1, w2, b2, g2, be2)
         wqkv16 = weight16(wq, wk, wv)
         Oh = None
         if fused:
-            if ATTN_F16:   # fp16 attention operand (the saved qkv: the backward recomputes from it)
-                qkv = torch.empty(NT, 3 * D, device=dev, dtype=torch.float16)
-                gemm(NT, 3 * D, D, op(x16, 0, D, True), op(wqkv16, 0, D, True), None, 3 * D, bias=bqkv, C16=qkv,
-                     c16_fp16=True)
-                Oh, O16, P, Pd = _attn16_fwd_f16(qkv, B, T, nh, dh, p_attn, seeds[0])
-            else:
-                qkv = torch.empty(NT, 3 * D, device=dev, dtype=BF16)     # bf16 only: attention operand
-                gemm(NT, 3 * D, D, op(x16, 0, D, True), op(wqkv16, 0, D, True), None, 3 * D, bias=bqkv, C16=qkv)
-                # P slot: lse2, Pd slot: the dropout keep bits for the backward
-                O16, P, Pd = _attn16_fwd(qkv, B, T, nh, dh, p_attn, seeds[0], want_mask=True)
+            # fp16 attention operand (the saved qkv: the backward recomputes from it); P slot: lse2,
+            # Pd slot: the dropout keep bits for the backward
+            qkv = torch.empty(NT, 3 * D, device=dev, dtype=torch.float16)
+            gemm(NT, 3 * D, D, op(x16, 0, D, True), op(wqkv16, 0, D, True), None, 3 * D, bias=bqkv, C16=qkv,
+                 c16_fp16=True)
+            Oh, O16, P, Pd = _attn16_fwd_f16(qkv, B, T, nh, dh, p_attn, seeds[0])
         else:
             qkv = torch.empty(NT, 3 * D, device=dev)
             gemm(NT, 3 * D, D, op(x16, 0, D, True), op(wqkv16, 0, D, True), qkv, 3 * D, bias=bqkv)
@@ -3093,12 +2997,9 @@ def _ln_fwd_x16(x2d, g, b, eps, half, want32=True, want_b16=False):
     return y, y16, mean, rstd
 
 
-# Conformer attention block: LayerNorm + rotary in one launch (B2P_LN_ROT=0: LayerNorm with an fp32
-# output, then b2p_rotary16 in the forward and again in the backward)
-_LN_ROT = [os.environ.get("B2P_LN_ROT", "1") != "0"]
-
-
 def ln_rotary16_ok(D, hd) -> bool:
+    """Conformer attention block: LayerNorm + rotary in one launch (otherwise LayerNorm with an fp32
+    output, then b2p_rotary16 in the forward and again in the backward)."""
     return D % 256 == 0 and D <= 1024 and hd in (32, 64, 128, 256) and D % hd == 0
 
 
@@ -3144,9 +3045,7 @@ def _act_dropout_cast16(pre, act, p, seed):
     return out
 
 
-_FFN_F16B = [os.environ.get("B2P_FFN_F16B", "1") != "0"]
-_BN16 = [os.environ.get("B2P_BN16", "1") != "0"]
-_FFN_PRE16 = [os.environ.get("B2P_FFN_PRE16", "1") != "0"]
+_BN16 = [True]   # False (tests): the Conformer conv module's BatchNorm output in fp32, operands cast from it
 
 
 @_gate_aware
@@ -3172,19 +3071,18 @@ class _FFNBlock(torch.autograd.Function):
             # recomputed from pre, a 195 MB pass per FFN at Conformer-large bs=32)
             half = _state.fwd16
             # the pre-activation is read only by the backward's act' (the GEMM epilogue's aux16 operand):
-            # stored in bf16 (B2P_FFN_PRE16=0: fp32), half the bytes written and read back
-            pre16 = _FFN_PRE16[0] and (not half or _FFN_F16B[0])
-            pre = torch.empty(NT, F, device=dev, dtype=BF16 if pre16 else torch.float32)
+            # stored in bf16, half the bytes of fp32 written and read back
+            pre = torch.empty(NT, F, device=dev, dtype=BF16)
             if half:   # h kept only as the bf16 weight-gradient operand of the backward (no fp32 copy)
                 _, h16, mean, rstd, h = _ln_fwd_x16(x2, g, b, eps, half, want32=False, want_b16=True)
             else:
                 _, h16, mean, rstd = _ln_fwd_x16(x2, g, b, eps, half, want32=False)
                 h = h16
             f = torch.empty(NT, F, device=dev, dtype=torch.float16 if half else BF16)
-            fb = torch.empty(NT, F, device=dev, dtype=BF16) if half and _FFN_F16B[0] else None
+            fb = torch.empty(NT, F, device=dev, dtype=BF16) if half else None
             w1b, w1op = _w_op16(w1, half)
-            gemm(NT, F, D, op(h16, 0, D, True), w1op, None, F, bias=b1, pre_out=None if pre16 else pre,
-                 pre16=pre if pre16 else None, act=act, drop_p=p_act, seed=s_act, C16=f, c16_fp16=half, C16b=fb)
+            gemm(NT, F, D, op(h16, 0, D, True), w1op, None, F, bias=b1, pre16=pre, act=act, drop_p=p_act, seed=s_act,
+                 C16=f, c16_fp16=half, C16b=fb)
             del h16, w1b
             w2b, w2op = _w_op16(w2, half)
             gemm(NT, D, F, op(f, 0, F, True), w2op, y, D, alpha=scale, bias=bs, drop_p=p_hid, seed=s_hid,
@@ -3324,16 +3222,14 @@ class _ConformerAttnBlock(torch.autograd.Function):
         # QKV GEMMs then write only the bf16 operand, and the saved slots hold qkv16 / lse2 / dropout
         # keep bits / O16
         ctx.fused = bf16_mode() and attn16_ok(T, hd)
-        # fused: the 16-bit attention operand (fp16 under ATTN_F16: the backward recomputes from it)
-        qkv = torch.empty(NT, 3 * D, device=dev, dtype=(torch.float16 if ATTN_F16 else BF16) if ctx.fused
-                          else torch.float32)
-        f16a = ctx.fused and ATTN_F16
+        # fused: the fp16 attention operand (the backward recomputes from it)
+        qkv = torch.empty(NT, 3 * D, device=dev, dtype=torch.float16 if ctx.fused else torch.float32)
         if bf16_mode():
             # the Q/K/V operands come straight from their producers as 16-bit copies (LayerNorm, rotary):
             # fp16 under forward_f16, else bf16; the fp32 rotated copy is never stored
             half = _state.fwd16
             hr16b = None
-            if cos_t is not None and _LN_ROT[0] and _bwd16_path() and ln_rotary16_ok(D, hd):
+            if cos_t is not None and _bwd16_path() and ln_rotary16_ok(D, hd):
                 # LayerNorm + rotary in one pass, 16-bit outputs only (no fp32 LN output, no rotary
                 # launches): the backward keeps the bf16 rotated copy for the Q/K weight gradients
                 h16, h16b, hr16, hr16b, mean, rstd = _ln_rotary16(x2, g, b, eps, T, hd, cos_t, sin_t, half)
@@ -3348,11 +3244,9 @@ class _ConformerAttnBlock(torch.autograd.Function):
             hr = None
             for i, (w, bb, src) in enumerate(((wq, bq, hr16), (wk, bk, hr16), (wv, bv, h16))):
                 wbuf, wop = _w_op16(w, half)
-                if f16a:
+                if ctx.fused:
                     gemm(NT, D, D, op(src, 0, D, True), wop, None, 3 * D, c_off=i * D, bias=bb, C16=qkv,
                          c16_fp16=True)
-                elif ctx.fused:
-                    gemm(NT, D, D, op(src, 0, D, True), wop, None, 3 * D, c_off=i * D, bias=bb, C16=qkv)
                 else:
                     gemm(NT, D, D, op(src, 0, D, True), wop, qkv, 3 * D, c_off=i * D, bias=bb)
                 del wbuf
@@ -3368,15 +3262,11 @@ class _ConformerAttnBlock(torch.autograd.Function):
             for i, (w, bb, src) in enumerate(((wq, bq, hr), (wk, bk, hr), (wv, bv, h))):
                 gemm(NT, D, D, op(src, 0, D, True), op(w, 0, D, True), qkv, 3 * D, c_off=i * D, bias=bb)
         y = torch.empty(NT, D, device=dev)
-        if f16a:
+        if ctx.fused:
             Oh, O, P, Pd = _attn16_fwd_f16(qkv, B, T, nh, hd, p_attn, seeds[0])
             wbuf, wop = _w_op16(wo, True)
             gemm(NT, D, D, op(Oh, 0, D, True), wop, y, D, bias=bo, drop_p=p_out, seed=seeds[1], residual=x2)
             del Oh, wbuf
-        elif ctx.fused:
-            O, P, Pd = _attn16_fwd(qkv, B, T, nh, hd, p_attn, seeds[0], want_mask=True)
-            gemm(NT, D, D, op(O, 0, D, True), op(weight16(wo), 0, D, True), y, D, bias=bo, drop_p=p_out,
-                 seed=seeds[1], residual=x2)
         else:
             P, Pd, O = _attn_core_fwd(qkv, B, T, nh, hd, p_attn, seeds[0])
             gemm(NT, D, D, op(O, 0, D, True), op(wo, 0, D, True), y, D, bias=bo, drop_p=p_out, seed=seeds[1],
@@ -3592,7 +3482,7 @@ class _ConvModule(torch.autograd.Function):
         sync = None
         # bf16 training step: the BatchNorm + activation writes only the 16-bit operands of pointwise conv 2
         # (its forward GEMM: fp16 under forward_f16; its weight gradient: bf16), no fp32 output and no cast
-        # passes (B2P_BN16=0: fp32 output, operands cast from it)
+        # passes (_BN16 False: fp32 output, operands cast from it)
         o16 = training and _BN16[0] and bf16_mode() and _bwd16_path() and D % 4 == 0
         half = o16 and _state.fwd16
         s = None if o16 else torch.empty(NT, D, device=dev)
@@ -3671,7 +3561,7 @@ class _ConvModule(torch.autograd.Function):
         du = torch.empty(NT, D, device=dev)
         ddw = None
         if ng[4]:
-            if _defer_ok(w_dw) and _LAZY_COLSUM:
+            if _defer_ok(w_dw):
                 _defer_dwconv_wgrad(w_dw, u, dc, B, T, D, K)   # frozen taps: their three launches on the side stream
             else:
                 ddw = torch.empty_like(w_dw)

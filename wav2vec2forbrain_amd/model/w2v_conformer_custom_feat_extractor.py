@@ -115,7 +115,7 @@ class Wav2Vec2ConformerEncoder(nn.Module):
     def forward(self, hidden_states):
         c = self.config
         hidden_states = Fn.dropout(hidden_states, c.hidden_dropout, self.training)
-        graph_ld = self.training and c.layerdrop > 0 and Fn.capturing() and Fn.GRAPH_LAYERDROP
+        graph_ld = self.training and c.layerdrop > 0 and Fn.capturing()
         for layer in self.layers:
             dropout_probability = torch.rand([])
             if graph_ld:   # captured step: device-drawn LayerDrop (Fn.layerdrop_layer)

@@ -123,7 +123,7 @@ class Wav2Vec2Encoder(nn.Module):
         # hidden = dropout(LN(x + gelu(posconv(x))))  (TF Wav2Vec2Encoder.forward)
         hidden_states = Fn.pos_conv_ln(hidden_states, g, v, cb, self.layer_norm.weight, self.layer_norm.bias,
                                        self.pos_conv_embed.groups, c.layer_norm_eps, c.hidden_dropout, self.training)
-        graph_ld = self.training and c.layerdrop > 0 and Fn.capturing() and Fn.GRAPH_LAYERDROP
+        graph_ld = self.training and c.layerdrop > 0 and Fn.capturing()
         for layer in self.layers:
             # LayerDrop: one CPU torch.rand([]) draw per layer, as the reference's encoder does; inside
             # a captured step the draw moves to the device (redrawn on every replay)
@@ -152,7 +152,7 @@ class Wav2Vec2EncoderStableLayerNorm(Wav2Vec2Encoder):
         g, v, cb = self.pos_conv_embed.weights()
         hidden_states = Fn.pos_conv_ln(hidden_states, g, v, cb, None, None, self.pos_conv_embed.groups,
                                        c.layer_norm_eps, c.hidden_dropout, self.training)
-        graph_ld = self.training and c.layerdrop > 0 and Fn.capturing() and Fn.GRAPH_LAYERDROP
+        graph_ld = self.training and c.layerdrop > 0 and Fn.capturing()
         for layer in self.layers:
             dropout_probability = torch.rand([])
             if graph_ld:
