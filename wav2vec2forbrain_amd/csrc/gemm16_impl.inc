@@ -270,8 +270,10 @@ __device__ __forceinline__ bf16x8 frag_t(const char* img, int col0, int kk, int 
 // B-operand = the A fragment), so each 16x16 accumulator tile is the TRANSPOSE of the output
 // block: lane l holds D[m][n .. n+3] with m = row0 + (l & 15), n = col0 + 4 (l >> 4) — four
 // consecutive output columns of one row. The epilogue then works and stores straight from the
-// accumulators: 16-B (fp32) / 8-B (16-bit) vector stores, 64 contiguous bytes per row per wave
-// instruction, no LDS staging, no barrier, no cross-lane traffic (except the fused column sums).
+// accumulators: 16-B vector stores, 64 contiguous bytes per row per wave instruction (fp32 images: one
+// column tile per store; 16-bit images: two, after a lane-group swap of the packed values, or 8-B stores of
+// one where the launch's alignment does not allow 16 B), no LDS staging, no barrier, no cross-lane traffic
+// (except that swap and the fused column sums).
 //
 // Every access goes through a raw buffer resource: an element outside the matrix gets the offset
 // OOB (past num_records), so its load returns 0 and its store is dropped by the hardware — loads and
@@ -314,6 +316,9 @@ __device__ __forceinline__ void bst16_wt(rsrc16_t r, uint32_t off, float4 v) {
 }
 __device__ __forceinline__ float4 bld16_sc1(rsrc16_t r, uint32_t off) {
   return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 16));
+}
+__device__ __forceinline__ void bst16u(rsrc16_t r, uint32_t off, uint4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), r, off, 0, 0);
 }
 __device__ __forceinline__ void bst8(rsrc16_t r, uint32_t off, uint2 v) {
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, v), r, off, 0, 0);
@@ -458,95 +463,152 @@ __device__ __forceinline__ void reg_epilogue(const EpiArgs& ea, const b2p_gemm_d
     const float alpha = e.alpha, beta = e.beta;
     const uint64_t sd = b2p_seed_eff(e.drop_seed, ea.epoch);
     const int act = e.act, act_bwd = e.act_bwd;
-    float4 cs[NJT] = {};
-    // per-element operands of one row tile (loaded one row tile ahead of its use)
-    float4 Lc[NJT], Lr[NJT], La[NJT];
-    auto load_row = [&](int i, float4 (&lc)[NJT], float4 (&lr)[NJT], float4 (&la)[NJT]) __attribute__((always_inline)) {
-      const int m = mrow0 + 16 * i + rl;
+    // 16-B form of the 16-bit images (W; ea.wide16, decided per launch on the host). The packed values of two
+    // adjacent column tiles j, j+1 trade 16-lane groups (v_permlane16_swap: groups 1 and 3 of tile j's
+    // register with groups 0 and 2 of tile j+1's), after which lane group g holds 8 consecutive columns of
+    // its row, 16 (j + (g & 1)) + 8 (g >> 1) .. + 7: one store instruction covers 16 rows x 64 contiguous
+    // bytes (the 8-B form: 16 rows x 32 B), half the store instructions for the same bytes. Values, and the
+    // order of the arithmetic on them, are those of the 8-B form. (aux16 read the same way, 16 B per lane and
+    // swapped back, measured no different from the 8-B loads: the backward kinds' tail is the GELU' arithmetic,
+    // profiles/r07a_epilogue_attribution.txt.)
+    const int cw = 16 * ((lane >> 4) & 1) + 8 * (lane >> 5);
+    auto swap2 = [](uint2& a, uint2& b) __attribute__((always_inline)) {
+      const auto x = __builtin_amdgcn_permlane16_swap(a.x, b.x, false, false);
+      const auto y = __builtin_amdgcn_permlane16_swap(a.y, b.y, false, false);
+      a = make_uint2(x[0], y[0]);
+      b = make_uint2(x[1], y[1]);
+    };
+    auto body = [&](auto wide) __attribute__((always_inline)) {
+      constexpr bool W = decltype(wide)::value;
+      float4 cs[NJT] = {};
+      // per-element operands of one row tile (loaded one row tile ahead of its use)
+      float4 Lc[NJT], Lr[NJT], La[NJT];
+      auto load_row = [&](int i, float4 (&lc)[NJT], float4 (&lr)[NJT], float4 (&la)[NJT]) __attribute__((always_inline)) {
+        const int m = mrow0 + 16 * i + rl;
 #pragma unroll
-      for (int j = 0; j < NJT; ++j) {
-        const int n = ncol0 + 16 * j + cq;
-        const bool ok = m < M && n < N;
-        if ((K & EK_BETA) != 0) lc[j] = bld16(rC, ok ? (uint32_t)(((int64_t)m * e.ldc + n) * 4) : OOB);
-        if ((K & EK_RES) != 0) lr[j] = bld16(rR, ok ? (uint32_t)(((int64_t)m * e.ldr + n) * 4) : OOB);
-        if ((K & EK_ABWD) != 0) {
-          if ((K & EK_AUX16) != 0)
-            la[j] = bf16x4_to_f4(bld8(rA, ok ? (uint32_t)(((int64_t)m * e.ldaux + n) * 2) : OOB));
-          else
-            la[j] = bld16(rA, ok ? (uint32_t)(((int64_t)m * e.ldaux + n) * 4) : OOB);
+        for (int j = 0; j < NJT; ++j) {
+          const int n = ncol0 + 16 * j + cq;
+          const bool ok = m < M && n < N;
+          if ((K & EK_BETA) != 0) lc[j] = bld16(rC, ok ? (uint32_t)(((int64_t)m * e.ldc + n) * 4) : OOB);
+          if ((K & EK_RES) != 0) lr[j] = bld16(rR, ok ? (uint32_t)(((int64_t)m * e.ldr + n) * 4) : OOB);
+          if ((K & EK_ABWD) != 0) {
+            if ((K & EK_AUX16) != 0)
+              la[j] = bf16x4_to_f4(bld8(rA, ok ? (uint32_t)(((int64_t)m * e.ldaux + n) * 2) : OOB));
+            else
+              la[j] = bld16(rA, ok ? (uint32_t)(((int64_t)m * e.ldaux + n) * 4) : OOB);
+          }
+        }
+      };
+      const bool LOADS = (K & (EK_BETA | EK_RES | EK_ABWD)) != 0;
+      // a runtime-kind wave of 8 row tiles has no registers for the one-row-ahead loads (they spilled)
+      constexpr bool AHEAD = !((EK & EK_RUNTIME) != 0 && MI > 4);
+      if (LOADS && AHEAD) load_row(0, Lc, Lr, La);
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        float4 Nc[NJT], Nr[NJT], Na[NJT];
+        if (LOADS) {
+          if (!AHEAD) load_row(i, Lc, Lr, La);
+          else if (i + 1 < MI) load_row(i + 1, Nc, Nr, Na);
+        }
+        const int m = mrow0 + 16 * i + rl;
+        const uint64_t drow = ((uint64_t)z * (uint64_t)M + (uint64_t)m) * (uint64_t)N;
+        uint2 hP[NJT], hC[NJT], hB[NJT];   // W: the packed 16-bit images of a tile pair, until its second tile is done
+#pragma unroll
+        for (int j = 0; j < NJT; ++j) {
+          const int n = ncol0 + 16 * j + cq;
+          const bool ok = m < M && n < N;
+          float v[4] = {alpha * acc[i][j][0], alpha * acc[i][j][1], alpha * acc[i][j][2], alpha * acc[i][j][3]};
+          if ((K & EK_BETA) != 0) {
+            v[0] += beta * Lc[j].x; v[1] += beta * Lc[j].y; v[2] += beta * Lc[j].z; v[3] += beta * Lc[j].w;
+          }
+          if ((K & EK_BIAS) != 0) {
+            v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w;
+          }
+          const uint32_t o4 = ok ? (uint32_t)(((int64_t)m * e.ldc + n) * 4) : OOB;
+          const uint32_t o2 = ok ? (uint32_t)(((int64_t)m * e.ldc + n) * 2) : OOB;
+          if ((K & EK_PRE32) != 0) bst16(rP32, o4, make_float4(v[0], v[1], v[2], v[3]));
+          if ((K & EK_PRE16) != 0) {
+            const uint2 h = b2p_pack_bf16x4(make_float4(v[0], v[1], v[2], v[3]));
+            if constexpr (W) hP[j] = h;
+            else bst8(rP16, o2, h);
+          }
+          if ((K & EK_ACT) != 0) {
+            if (act == B2P_ACT_GELU) {
+              const b2p_f2 g0 = b2p_gelu2(b2p_f2{v[0], v[1]}), g1 = b2p_gelu2(b2p_f2{v[2], v[3]});
+              v[0] = g0.x; v[1] = g0.y; v[2] = g1.x; v[3] = g1.y;
+            } else {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[q] = apply_act(v[q], act);
+            }
+          }
+          if ((K & EK_DROP) != 0) {
+            bool k[4];
+            b2p_keep4(sd, drow + (uint64_t)n, ea.drop_thr, k);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = k[q] ? v[q] * ea.drop_scale : 0.0f;
+          }
+          if ((K & EK_ABWD) != 0) {
+            if (act_bwd == B2P_ACT_GELU) {
+              const b2p_f2 g0 = b2p_gelu_grad2(b2p_f2{La[j].x, La[j].y}), g1 = b2p_gelu_grad2(b2p_f2{La[j].z, La[j].w});
+              v[0] *= g0.x; v[1] *= g0.y; v[2] *= g1.x; v[3] *= g1.y;
+            } else {
+              v[0] *= act_grad(La[j].x, act_bwd); v[1] *= act_grad(La[j].y, act_bwd);
+              v[2] *= act_grad(La[j].z, act_bwd); v[3] *= act_grad(La[j].w, act_bwd);
+            }
+          }
+          if ((K & EK_RES) != 0) {
+            v[0] += Lr[j].x; v[1] += Lr[j].y; v[2] += Lr[j].z; v[3] += Lr[j].w;
+          }
+          const float4 f = make_float4(v[0], v[1], v[2], v[3]);
+          if ((K & EK_C32) != 0) bst16(rC, o4, f);
+          if ((K & EK_C16) != 0) {
+            const uint2 h = (K & EK_C16H) != 0 ? b2p_pack_f16x4(f) : b2p_pack_bf16x4(f);
+            if constexpr (W) hC[j] = h;
+            else bst8(rC16, o2, h);
+          }
+          if ((K & EK_C16B) != 0) {
+            const uint2 h = b2p_pack_bf16x4(f);
+            if constexpr (W) hB[j] = h;
+            else bst8(rC16b, o2, h);
+          }
+          if constexpr (W) {
+            if (j & 1) {   // the pair (j - 1, j): 16 B per lane
+              const int n8 = ncol0 + 16 * (j - 1) + cw;
+              const uint32_t ow = (m < M && n8 < N) ? (uint32_t)(((int64_t)m * e.ldc + n8) * 2) : OOB;
+              if ((K & EK_PRE16) != 0) {
+                swap2(hP[j - 1], hP[j]);
+                bst16u(rP16, ow, make_uint4(hP[j - 1].x, hP[j - 1].y, hP[j].x, hP[j].y));
+              }
+              if ((K & EK_C16) != 0) {
+                swap2(hC[j - 1], hC[j]);
+                bst16u(rC16, ow, make_uint4(hC[j - 1].x, hC[j - 1].y, hC[j].x, hC[j].y));
+              }
+              if ((K & EK_C16B) != 0) {
+                swap2(hB[j - 1], hB[j]);
+                bst16u(rC16b, ow, make_uint4(hB[j - 1].x, hB[j - 1].y, hB[j].x, hB[j].y));
+              }
+            }
+          }
+          if constexpr ((EK & EK_CSUM) != 0) {
+            if (ok) { cs[j].x += f.x; cs[j].y += f.y; cs[j].z += f.z; cs[j].w += f.w; }
+          }
+        }
+        if (LOADS && AHEAD) {
+#pragma unroll
+          for (int j = 0; j < NJT; ++j) { Lc[j] = Nc[j]; Lr[j] = Nr[j]; La[j] = Na[j]; }
+        }
+        if constexpr ((EK & EK_CSUM) != 0) {   // the host never hands column sums to EK_RUNTIME
+          if (i & 1) colsum_band(cs, i >> 1);
         }
       }
     };
-    const bool LOADS = (K & (EK_BETA | EK_RES | EK_ABWD)) != 0;
-    // a runtime-kind wave of 8 row tiles has no registers for the one-row-ahead loads (they spilled)
-    constexpr bool AHEAD = !((EK & EK_RUNTIME) != 0 && MI > 4);
-    if (LOADS && AHEAD) load_row(0, Lc, Lr, La);
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-      float4 Nc[NJT], Nr[NJT], Na[NJT];
-      if (LOADS) {
-        if (!AHEAD) load_row(i, Lc, Lr, La);
-        else if (i + 1 < MI) load_row(i + 1, Nc, Nr, Na);
-      }
-      const int m = mrow0 + 16 * i + rl;
-      const uint64_t drow = ((uint64_t)z * (uint64_t)M + (uint64_t)m) * (uint64_t)N;
-#pragma unroll
-      for (int j = 0; j < NJT; ++j) {
-        const int n = ncol0 + 16 * j + cq;
-        const bool ok = m < M && n < N;
-        float v[4] = {alpha * acc[i][j][0], alpha * acc[i][j][1], alpha * acc[i][j][2], alpha * acc[i][j][3]};
-        if ((K & EK_BETA) != 0) {
-          v[0] += beta * Lc[j].x; v[1] += beta * Lc[j].y; v[2] += beta * Lc[j].z; v[3] += beta * Lc[j].w;
-        }
-        if ((K & EK_BIAS) != 0) {
-          v[0] += bias4[j].x; v[1] += bias4[j].y; v[2] += bias4[j].z; v[3] += bias4[j].w;
-        }
-        const uint32_t o4 = ok ? (uint32_t)(((int64_t)m * e.ldc + n) * 4) : OOB;
-        const uint32_t o2 = ok ? (uint32_t)(((int64_t)m * e.ldc + n) * 2) : OOB;
-        if ((K & EK_PRE32) != 0) bst16(rP32, o4, make_float4(v[0], v[1], v[2], v[3]));
-        if ((K & EK_PRE16) != 0) bst8(rP16, o2, b2p_pack_bf16x4(make_float4(v[0], v[1], v[2], v[3])));
-        if ((K & EK_ACT) != 0) {
-          if (act == B2P_ACT_GELU) {
-            const b2p_f2 g0 = b2p_gelu2(b2p_f2{v[0], v[1]}), g1 = b2p_gelu2(b2p_f2{v[2], v[3]});
-            v[0] = g0.x; v[1] = g0.y; v[2] = g1.x; v[3] = g1.y;
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = apply_act(v[q], act);
-          }
-        }
-        if ((K & EK_DROP) != 0) {
-          bool k[4];
-          b2p_keep4(sd, drow + (uint64_t)n, ea.drop_thr, k);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = k[q] ? v[q] * ea.drop_scale : 0.0f;
-        }
-        if ((K & EK_ABWD) != 0) {
-          if (act_bwd == B2P_ACT_GELU) {
-            const b2p_f2 g0 = b2p_gelu_grad2(b2p_f2{La[j].x, La[j].y}), g1 = b2p_gelu_grad2(b2p_f2{La[j].z, La[j].w});
-            v[0] *= g0.x; v[1] *= g0.y; v[2] *= g1.x; v[3] *= g1.y;
-          } else {
-            v[0] *= act_grad(La[j].x, act_bwd); v[1] *= act_grad(La[j].y, act_bwd);
-            v[2] *= act_grad(La[j].z, act_bwd); v[3] *= act_grad(La[j].w, act_bwd);
-          }
-        }
-        if ((K & EK_RES) != 0) {
-          v[0] += Lr[j].x; v[1] += Lr[j].y; v[2] += Lr[j].z; v[3] += Lr[j].w;
-        }
-        const float4 f = make_float4(v[0], v[1], v[2], v[3]);
-        if ((K & EK_C32) != 0) bst16(rC, o4, f);
-        if ((K & EK_C16) != 0) bst8(rC16, o2, (K & EK_C16H) != 0 ? b2p_pack_f16x4(f) : b2p_pack_bf16x4(f));
-        if ((K & EK_C16B) != 0) bst8(rC16b, o2, b2p_pack_bf16x4(f));
-        if constexpr ((EK & EK_CSUM) != 0) {
-          if (ok) { cs[j].x += f.x; cs[j].y += f.y; cs[j].z += f.z; cs[j].w += f.w; }
-        }
-      }
-      if (LOADS && AHEAD) {
-#pragma unroll
-        for (int j = 0; j < NJT; ++j) { Lc[j] = Nc[j]; Lr[j] = Nr[j]; La[j] = Na[j]; }
-      }
-      if constexpr ((EK & EK_CSUM) != 0) {   // the host never hands column sums to EK_RUNTIME
-        if (i & 1) colsum_band(cs, i >> 1);
-      }
+    // the runtime kind keeps the 8-B form: with both forms in it, it spilled (68-84 bytes of scratch per lane)
+    constexpr bool WIDE_OK = NJT % 2 == 0 && (EK & EK_RUNTIME) == 0 && (EK & (EK_C16 | EK_C16B | EK_PRE16)) != 0;
+    if constexpr (WIDE_OK) {
+      if (ea.wide16) body(std::true_type{});
+      else body(std::false_type{});
+    } else {
+      body(std::false_type{});
     }
   }
 }

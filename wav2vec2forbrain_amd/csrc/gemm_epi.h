@@ -28,6 +28,7 @@ struct EpiArgs {
   uint32_t drop_thr;
   float drop_scale;
   int32_t vec4;   // every C-shaped tensor allows 16-B (C16: 8-B) accesses at n % 4 == 0
+  int32_t wide16; // vec4, and every 16-bit output image (C16, C16b, pre16) allows 16-B stores at n % 8 == 0
   const uint64_t* epoch;   // graph-replay dropout seed offset (b2p_seed_eff)
   const int32_t* gate;     // LayerDrop gate (b2p_gate): closed -> no K loop
   const int64_t* gates;    // per batch member z1: the member's gate pointer (b2p_gate_batch; 0 = open), or NULL
@@ -196,6 +197,9 @@ inline EpiArgs make_epi_args(const b2p_gemm_desc& d) {
   if (e.C16b) v = v && ((uintptr_t)e.C16b & 7u) == 0;
   if (e.residual) v = v && a16(e.residual) && s4(e.ldr) && s4(e.rbs1) && s4(e.rbs2);
   ea.vec4 = v ? 1 : 0;
+  // the gemm16 register epilogue's 16-B stores of the 16-bit images (two column tiles per store)
+  auto s8 = [](int64_t x) { return x % 8 == 0; };
+  ea.wide16 = v && d.N % 8 == 0 && s8(e.ldc) && s8(e.cbs1) && s8(e.cbs2) && a16(e.C16) && a16(e.C16b) && a16(e.pre16);
   ea.epoch = b2p_seed_epoch();
   ea.gate = b2p_gate();
   ea.gates = b2p_gate_batch();
