@@ -139,6 +139,9 @@ int b2p_set_gate(const int32_t* dev_flag);
 /* *flag = keep (1) / skip (0) of one layer for this replay: the draw b2p_layerdrop_select makes for
  * the same (p, seed) (step counter of b2p_set_seed_epoch mixed in). */
 int b2p_layerdrop_flag(int32_t* flag, float p, uint64_t seed, b2p_stream_t stream);
+/* flags[i] = the b2p_layerdrop_flag draw of seeds[i], i < n, for all layers of one encoder forward in
+ * one launch (seeds: host array, carried by value; one more launch per 32 layers beyond the first 32). */
+int b2p_layerdrop_flags(int32_t* flags, const uint64_t* seeds, int64_t n, float p, b2p_stream_t stream);
 int b2p_seed_epoch_step(uint64_t* dev_counter, b2p_stream_t stream);
 
 /* ------------------------------------------------------------------ elementwise / reductions */
@@ -219,6 +222,29 @@ int b2p_layernorm_bwd_acc2(const float* dy, const float* x, const float* gamma, 
                            int64_t cols, const float* dx_accum, const float* dx_accum2, float drop_p,
                            uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
                            float* dbias_in, uint16_t* d16, float* workspace, b2p_stream_t stream);
+/* LayerDrop's select and route folded into a layer's own LayerNorm launches (gates: device int32 flags
+ * as b2p_set_gate's, 0 = closed, read when the kernel runs; a NULL gate gives the ungated call).
+ * b2p_layernorm_fwd16_sel / b2p_layernorm_fwd_x16_sel: under a closed gate y, y16 and y16b receive
+ * skip, skip16 and skip16b (the layer input and its 16-bit images; a NULL 16-bit source is packed
+ * from skip) instead of the normalised values; mean / rstd stay those of x.
+ * b2p_layernorm_bwd_gated: a closed dy_gate stands for dy = 0 (dy is not read); with acc2_gate the
+ * addend is dx_accum2 under a closed gate and +0 under an open one (the add is always performed).
+ * Bit for bit the results of b2p_layerdrop_select_h after the LayerNorm, and of b2p_layerdrop_route
+ * before b2p_layernorm_bwd_acc2. */
+int b2p_layernorm_fwd16_sel(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y16,
+                            float* mean, float* rstd, int64_t rows, int64_t cols, float eps, float drop_p,
+                            uint64_t drop_seed, const int32_t* gate, const float* skip, const uint16_t* skip16,
+                            b2p_stream_t stream);
+int b2p_layernorm_fwd_x16_sel(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y16,
+                              int y16_fp16, uint16_t* y16b, float* mean, float* rstd, int64_t rows, int64_t cols,
+                              float eps, const int32_t* gate, const float* skip, const uint16_t* skip16,
+                              const uint16_t* skip16b, b2p_stream_t stream);
+int b2p_layernorm_bwd_gated(const float* dy, const float* x, const float* gamma, const float* mean,
+                            const float* rstd, float* dx, float* dgamma, float* dbeta, int64_t rows,
+                            int64_t cols, const float* dx_accum, const float* dx_accum2, float drop_p,
+                            uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
+                            float* dbias_in, uint16_t* d16, const int32_t* dy_gate, const int32_t* acc2_gate,
+                            float* workspace, b2p_stream_t stream);
 
 /* fp32 -> bf16 (round to nearest even), the GEMM operand copy of a weight or activation
  * (master copies stay fp32; replaces the implicit .to(bfloat16) of autocast) */

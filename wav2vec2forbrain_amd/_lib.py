@@ -184,6 +184,13 @@ _SIGS = {
     "b2p_layerdrop_route": (c_i32, [c_p, c_p, c_p, c_i64, c_f32, c_u64, c_p]),
     "b2p_set_gate": (c_i32, [c_p]),
     "b2p_layerdrop_flag": (c_i32, [c_p, c_f32, c_u64, c_p]),
+    "b2p_layerdrop_flags": (c_i32, [c_p, ctypes.POINTER(c_u64), c_i64, c_f32, c_p]),
+    "b2p_layernorm_fwd16_sel": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_f32, c_u64, c_p, c_p,
+                                        c_p, c_p]),
+    "b2p_layernorm_fwd_x16_sel": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p,
+                                          c_p, c_p, c_p]),
+    "b2p_layernorm_bwd_gated": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_f32, c_u64,
+                                        c_p, c_f32, c_u64, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
 # timing families (b2p_timing_*)

@@ -440,8 +440,15 @@ __global__ void __launch_bounds__(256) ln_fwd_k(const float* __restrict__ x, con
                                                 int64_t rows, int cols, float eps, uint32_t thr, float dscale,
                                                 uint64_t seed, float drop_p, uint16_t* __restrict__ y16,
                                                 const uint64_t* __restrict__ epoch, int y16_half = 0,
-                                                uint16_t* __restrict__ y16b = nullptr) {
+                                                uint16_t* __restrict__ y16b = nullptr,
+                                                const int32_t* __restrict__ gate = nullptr,
+                                                const float* __restrict__ skip = nullptr,
+                                                const uint16_t* __restrict__ skip16 = nullptr,
+                                                const uint16_t* __restrict__ skip16b = nullptr) {
   seed = b2p_seed_eff(seed, epoch);
+  // LayerDrop select folded into a layer's last LayerNorm: a closed gate writes the layer input (skip,
+  // with its 16-bit images) instead of the normalised values; read once per block (uniform)
+  const bool closed = b2p_gated_off(gate);
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -470,6 +477,26 @@ __global__ void __launch_bounds__(256) ln_fwd_k(const float* __restrict__ x, con
   const float4* g4 = reinterpret_cast<const float4*>(gamma);
   const float4* b4 = reinterpret_cast<const float4*>(beta);
   float4* yr = reinterpret_cast<float4*>(y + row * cols);
+  if (closed) {
+    // the statistics above stay those of x (the layer's gated backward reads them: finite, as when
+    // ld_select_k overwrote y afterwards); a missing 16-bit source is packed from the fp32 one
+    const float4* sr = reinterpret_cast<const float4*>(skip + row * cols);
+#pragma unroll
+    for (int i = 0; i < LN_MAXV; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nv) {
+        const float4 o = sr[c];
+        if (y) yr[c] = o;
+        if (y16)
+          reinterpret_cast<uint2*>(y16 + row * cols)[c] =
+              skip16 ? reinterpret_cast<const uint2*>(skip16 + row * cols)[c] : b2p_pack16x4(o, y16_half);
+        if (y16b)
+          reinterpret_cast<uint2*>(y16b + row * cols)[c] =
+              skip16b ? reinterpret_cast<const uint2*>(skip16b + row * cols)[c] : b2p_pack_bf16x4(o);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
     const int c = lane + 64 * i;
@@ -588,9 +615,16 @@ __global__ void __launch_bounds__(256) ln_bwd_k(const float* __restrict__ dy, co
                                                 int64_t rows, int cols, uint32_t thr, float dscale, uint64_t seed,
                                                 float drop_p, float* __restrict__ dxd, uint32_t thr2, float dscale2,
                                                 uint64_t seed2, uint16_t* __restrict__ d16, const uint64_t* __restrict__ epoch,
-                                                const float* __restrict__ dx_accum2) {
+                                                const float* __restrict__ dx_accum2,
+                                                const int32_t* __restrict__ dy_gate,
+                                                const int32_t* __restrict__ acc2_gate) {
   seed = b2p_seed_eff(seed, epoch);
   seed2 = b2p_seed_eff(seed2, epoch);
+  // LayerDrop route folded in (both uniform, read once per block): a closed dy_gate stands for dy = 0
+  // without loading it; dx_accum2 under acc2_gate is added only when that gate is closed (+0 otherwise:
+  // the add is always performed, so the bits are those of the routed zero-filled tensors)
+  const bool dy_off = b2p_gated_off(dy_gate);
+  const bool a2_on = !acc2_gate || *acc2_gate == 0;
   __shared__ float red[4][3][LN_MAXV * 256];   // cols <= 1024
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nv = cols >> 2;
@@ -611,10 +645,11 @@ __global__ void __launch_bounds__(256) ln_bwd_k(const float* __restrict__ dy, co
     for (int i = 0; i < LN_MAXV; ++i) {
       const int c = lane + 64 * i;
       if (c < nv && r < rows) {
-        nd[i] = reinterpret_cast<const float4*>(dy + r * cols)[c];
+        nd[i] = dy_off ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4*>(dy + r * cols)[c];
         nx[i] = reinterpret_cast<const float4*>(x + r * cols)[c];
         if (MODE & LNB_A1) na[i] = reinterpret_cast<const float4*>(dx_accum + r * cols)[c];
-        if (MODE & LNB_A2) nb[i] = reinterpret_cast<const float4*>(dx_accum2 + r * cols)[c];
+        if (MODE & LNB_A2)
+          nb[i] = a2_on ? reinterpret_cast<const float4*>(dx_accum2 + r * cols)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
   };
@@ -1135,13 +1170,25 @@ extern "C" int b2p_dropout(const float* x, float* y, int64_t n, float p, uint64_
 extern "C" int b2p_layernorm_fwd16(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y16,
                                    float* mean, float* rstd, int64_t rows, int64_t cols, float eps, float drop_p,
                                    uint64_t drop_seed, b2p_stream_t stream) {
+  return b2p_layernorm_fwd16_sel(x, gamma, beta, y, y16, mean, rstd, rows, cols, eps, drop_p, drop_seed, nullptr,
+                                 nullptr, nullptr, stream);
+}
+
+extern "C" int b2p_layernorm_fwd16_sel(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y16,
+                                       float* mean, float* rstd, int64_t rows, int64_t cols, float eps,
+                                       float drop_p, uint64_t drop_seed, const int32_t* gate, const float* skip,
+                                       const uint16_t* skip16, b2p_stream_t stream) {
   B2P_CHECK_ARG(x && gamma && beta && y && mean && rstd, "layernorm_fwd: NULL pointer");
   B2P_CHECK_ARG(cols % 4 == 0 && cols <= 64 * 4 * LN_MAXV, "layernorm_fwd: cols must be %%4 and <= 1024");
   B2P_CHECK_ARG(((uintptr_t)y16 & 7u) == 0, "layernorm_fwd: y16 must be 8-byte aligned");
+  B2P_CHECK_ARG(!gate || skip, "layernorm_fwd: a gate needs the skip source");
+  B2P_CHECK_ARG(((uintptr_t)skip & 15u) == 0 && ((uintptr_t)skip16 & 7u) == 0,
+                "layernorm_fwd: skip must be 16-byte, skip16 8-byte aligned");
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(ln_fwd_k, dim3(nblocks(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
                      mean, rstd, rows, (int)cols, eps, b2p_dropout_threshold(drop_p),
-                     drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, drop_seed, drop_p, y16, b2p_seed_epoch());
+                     drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, drop_seed, drop_p, y16, b2p_seed_epoch(), 0,
+                     (uint16_t*)nullptr, gate, skip, skip16, (const uint16_t*)nullptr);
   B2P_CHECK_LAUNCH();
   return 0;
 }
@@ -1149,14 +1196,26 @@ extern "C" int b2p_layernorm_fwd16(const float* x, const float* gamma, const flo
 extern "C" int b2p_layernorm_fwd_x16(const float* x, const float* gamma, const float* beta, float* y, uint16_t* y16,
                                      int y16_fp16, uint16_t* y16b, float* mean, float* rstd, int64_t rows,
                                      int64_t cols, float eps, b2p_stream_t stream) {
+  return b2p_layernorm_fwd_x16_sel(x, gamma, beta, y, y16, y16_fp16, y16b, mean, rstd, rows, cols, eps, nullptr,
+                                   nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int b2p_layernorm_fwd_x16_sel(const float* x, const float* gamma, const float* beta, float* y,
+                                         uint16_t* y16, int y16_fp16, uint16_t* y16b, float* mean, float* rstd,
+                                         int64_t rows, int64_t cols, float eps, const int32_t* gate,
+                                         const float* skip, const uint16_t* skip16, const uint16_t* skip16b,
+                                         b2p_stream_t stream) {
   B2P_CHECK_ARG(x && gamma && beta && y16 && mean && rstd, "layernorm_fwd_x16: NULL pointer");
+  B2P_CHECK_ARG(!gate || skip, "layernorm_fwd_x16: a gate needs the skip source");
+  B2P_CHECK_ARG(((uintptr_t)skip & 15u) == 0 && ((uintptr_t)skip16 & 7u) == 0 && ((uintptr_t)skip16b & 7u) == 0,
+                "layernorm_fwd_x16: skip must be 16-byte, skip16 / skip16b 8-byte aligned");
   B2P_CHECK_ARG(cols % 4 == 0 && cols <= 64 * 4 * LN_MAXV, "layernorm_fwd_x16: cols must be %%4 and <= 1024");
   B2P_CHECK_ARG(((uintptr_t)y16 & 7u) == 0 && ((uintptr_t)y16b & 7u) == 0,
                 "layernorm_fwd_x16: y16 / y16b must be 8-byte aligned");
   if (rows <= 0) return 0;
   hipLaunchKernelGGL(ln_fwd_k, dim3(nblocks(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
                      mean, rstd, rows, (int)cols, eps, 0u, 1.f, (uint64_t)0, 0.f, y16, b2p_seed_epoch(),
-                     y16_fp16 ? 1 : 0, y16b);
+                     y16_fp16 ? 1 : 0, y16b, gate, skip, skip16, skip16b);
   B2P_CHECK_LAUNCH();
   return 0;
 }
@@ -1201,7 +1260,7 @@ extern "C" int b2p_layernorm_fwd(const float* x, const float* gamma, const float
 namespace {
 typedef void (*LnBwdKernel)(const float*, const float*, const float*, const float*, const float*, float*, const float*,
                             float*, int64_t, int, uint32_t, float, uint64_t, float, float*, uint32_t, float, uint64_t,
-                            uint16_t*, const uint64_t*, const float*);
+                            uint16_t*, const uint64_t*, const float*, const int32_t*, const int32_t*);
 LnBwdKernel ln_bwd_kernel(int mode) {
   switch (mode) {
     case 0: return ln_bwd_k<true, 0>;
@@ -1235,6 +1294,17 @@ extern "C" int b2p_layernorm_bwd_acc2(const float* dy, const float* x, const flo
                                       int64_t cols, const float* dx_accum, const float* dx_accum2, float drop_p,
                                       uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
                                       float* dbias_in, uint16_t* d16, float* workspace, b2p_stream_t stream) {
+  return b2p_layernorm_bwd_gated(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, cols, dx_accum, dx_accum2, drop_p,
+                                 drop_seed, dx_dropped, in_drop_p, in_drop_seed, dbias_in, d16, nullptr, nullptr,
+                                 workspace, stream);
+}
+
+extern "C" int b2p_layernorm_bwd_gated(const float* dy, const float* x, const float* gamma, const float* mean,
+                                       const float* rstd, float* dx, float* dgamma, float* dbeta, int64_t rows,
+                                       int64_t cols, const float* dx_accum, const float* dx_accum2, float drop_p,
+                                       uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
+                                       float* dbias_in, uint16_t* d16, const int32_t* dy_gate,
+                                       const int32_t* acc2_gate, float* workspace, b2p_stream_t stream) {
   B2P_CHECK_ARG(dy && x && gamma && mean && rstd && dx && workspace, "layernorm_bwd: NULL pointer");
   B2P_CHECK_ARG(cols % 4 == 0 && cols <= 64 * 4 * LN_MAXV, "layernorm_bwd: cols must be %%4 and <= 1024");
   B2P_CHECK_ARG(((uintptr_t)d16 & 7u) == 0, "layernorm_bwd: d16 must be 8-byte aligned");
@@ -1245,7 +1315,8 @@ extern "C" int b2p_layernorm_bwd_acc2(const float* dy, const float* x, const flo
   hipLaunchKernelGGL(ln_bwd_kernel(mode), dim3(nblk), dim3(256), 0, st, dy, x, gamma, mean, rstd, dx, dx_accum, workspace,
                      rows, (int)cols, b2p_dropout_threshold(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f,
                      drop_seed, drop_p, dx_dropped, b2p_dropout_threshold(in_drop_p),
-                     in_drop_p > 0.f ? 1.f / (1.f - in_drop_p) : 1.f, in_drop_seed, d16, b2p_seed_epoch(), dx_accum2);
+                     in_drop_p > 0.f ? 1.f / (1.f - in_drop_p) : 1.f, in_drop_seed, d16, b2p_seed_epoch(), dx_accum2,
+                     dy_gate, dx_accum2 ? acc2_gate : nullptr);
   // partials [nblk][3][cols] -> dgamma | dbeta | dbias_in in one launch
   B2P_CHECK_ARG(((uintptr_t)dgamma & 15u) == 0 && ((uintptr_t)dbeta & 15u) == 0 && ((uintptr_t)dbias_in & 15u) == 0,
                 "layernorm_bwd: dgamma / dbeta / dbias_in must be 16-byte aligned");

@@ -77,6 +77,23 @@ __global__ void ld_flag_k(int32_t* flag, uint32_t thr, uint64_t seed, const uint
   if (threadIdx.x == 0) *flag = dev_keep(seed, epoch, thr) ? 1 : 0;
 }
 
+// the gates of all layers of one encoder forward in one launch: flags[i] = the draw ld_flag_k makes for
+// seeds.s[i]. Seeds travel by value (a captured graph keeps them); thread i picks its own with constant
+// indices, so the struct stays in the kernel arguments.
+constexpr int LD_FLAGS_MAX = 32;
+struct LdSeeds {
+  uint64_t s[LD_FLAGS_MAX];
+};
+__global__ void __launch_bounds__(64) ld_flags_k(int32_t* __restrict__ flags, LdSeeds seeds, int n, uint32_t thr,
+                                                 const uint64_t* __restrict__ epoch) {
+  const int t = threadIdx.x;
+  uint64_t seed = 0;
+#pragma unroll
+  for (int j = 0; j < LD_FLAGS_MAX; ++j)
+    if (j == t) seed = seeds.s[j];
+  if (t < n) flags[t] = dev_keep(seed, epoch, thr) ? 1 : 0;
+}
+
 inline unsigned grid_for(int64_t n4) {
   const int64_t b = (n4 + 255) / 256;
   return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
@@ -141,6 +158,20 @@ extern "C" int b2p_layerdrop_flag(int32_t* flag, float p, uint64_t seed, b2p_str
   B2P_CHECK_ARG(p >= 0.f && p < 1.f, "layerdrop_flag: p must be in [0,1)");
   hipLaunchKernelGGL(ld_flag_k, dim3(1), dim3(64), 0, (hipStream_t)stream, flag, b2p_dropout_threshold(p), seed,
                      b2p_seed_epoch());
+  B2P_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int b2p_layerdrop_flags(int32_t* flags, const uint64_t* seeds, int64_t n, float p, b2p_stream_t stream) {
+  B2P_CHECK_ARG(n <= 0 || (flags && seeds), "layerdrop_flags: NULL pointer");
+  B2P_CHECK_ARG(p >= 0.f && p < 1.f, "layerdrop_flags: p must be in [0,1)");
+  for (int64_t l0 = 0; l0 < n; l0 += LD_FLAGS_MAX) {   // beyond the struct's capacity: one launch per 32 layers
+    const int nl = (int)(n - l0 < LD_FLAGS_MAX ? n - l0 : LD_FLAGS_MAX);
+    LdSeeds s{};
+    for (int j = 0; j < nl; ++j) s.s[j] = seeds[l0 + j];
+    hipLaunchKernelGGL(ld_flags_k, dim3(1), dim3(64), 0, (hipStream_t)stream, flags + l0, s, nl,
+                       b2p_dropout_threshold(p), b2p_seed_epoch());
+  }
   B2P_CHECK_LAUNCH();
   return 0;
 }

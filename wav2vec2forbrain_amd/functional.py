@@ -1177,11 +1177,16 @@ def _act_bwd(dy, pre, act, out=None):
     return out
 
 
-def _ln_fwd(x2d, g, b, eps, drop_p=0.0, seed=0):
+def _ln_fwd(x2d, g, b, eps, drop_p=0.0, seed=0, sel=None):
+    """sel (LayerDrop's forward select folded in, _ld_sel): (gate, skip, ...); y is skip under a closed gate."""
     rows, cols = x2d.shape
     y = torch.empty_like(x2d)
     mean = torch.empty(rows, device=x2d.device)
     rstd = torch.empty(rows, device=x2d.device)
+    if sel is not None:
+        _lib.call("b2p_layernorm_fwd16_sel", _p(x2d), _p(g), _p(b), _p(y), None, _p(mean), _p(rstd), rows, cols,
+                  float(eps), float(drop_p), seed, _p(sel[0]), _p(sel[1]), None, _st())
+        return y, mean, rstd
     _lib.call("b2p_layernorm_fwd", _p(x2d), _p(g), _p(b), _p(y), _p(mean), _p(rstd), rows, cols, float(eps),
               float(drop_p), seed, _st())
     return y, mean, rstd
@@ -1204,8 +1209,9 @@ def _ln_parts(ws, rows, cols, q):
 
 
 def _ln_bwd(dy, x, g, mean, rstd, need_params=True, dx_accum=None, drop_p=0.0, seed=0, in_drop_p=-1.0,
-            in_seed=0, dbias_in=None, dx_accum2=None, lazy=None):
+            in_seed=0, dbias_in=None, dx_accum2=None, lazy=None, dy_gate=None, acc2_gate=None):
     """dx_accum2: a second accumulator added to dx alone (LayerDrop's skip gradient, _skip_take).
+    dy_gate / acc2_gate: LayerDrop's route folded in, as in _ln_bwd16 (b2p_layernorm_bwd_gated).
     lazy (see _ln_lazy): dg / db come back as ColsumParts (no ln_param_reduce launch on the main stream),
     and the result gains a fifth entry, the dropout-input bias gradient (dbias_in or its ColsumParts)."""
     rows, cols = x.shape
@@ -1215,9 +1221,14 @@ def _ln_bwd(dy, x, g, mean, rstd, need_params=True, dx_accum=None, drop_p=0.0, s
     db = torch.empty(cols, device=x.device) if need_params and not lz else None
     ws = torch.empty(int(_lib.load().b2p_layernorm_bwd_workspace(rows, cols)), device=x.device)
     dxd = torch.empty_like(x) if in_drop_p >= 0.0 else None
-    _lib.call("b2p_layernorm_bwd_acc2", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
-              cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, _p(dxd), float(max(in_drop_p, 0.0)), in_seed,
-              None if lz else _p(dbias_in), None, _p(ws), _st())
+    if dy_gate is not None or acc2_gate is not None:
+        _lib.call("b2p_layernorm_bwd_gated", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
+                  cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, _p(dxd), float(max(in_drop_p, 0.0)),
+                  in_seed, None if lz else _p(dbias_in), None, _p(dy_gate), _p(acc2_gate), _p(ws), _st())
+    else:
+        _lib.call("b2p_layernorm_bwd_acc2", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
+                  cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, _p(dxd), float(max(in_drop_p, 0.0)),
+                  in_seed, None if lz else _p(dbias_in), None, _p(ws), _st())
     if lz:
         dg, db = _ln_parts(ws, rows, cols, 0), _ln_parts(ws, rows, cols, 1)
         dbias_in = _ln_parts(ws, rows, cols, 2) if dbias_in is not None else None
@@ -1399,21 +1410,28 @@ def to16h(x):
     return out
 
 
-def _ln_fwd16(x2d, g, b, eps, drop_p=0.0, seed=0):
+def _ln_fwd16(x2d, g, b, eps, drop_p=0.0, seed=0, sel=None):
+    """sel (LayerDrop's forward select folded in, _ld_sel): (gate, skip, skip16 or None); under a closed
+    gate y / y16 are skip / its bf16 image instead of the normalised values."""
     rows, cols = x2d.shape
     y = torch.empty_like(x2d)
     y16 = torch.empty(rows, cols, device=x2d.device, dtype=BF16)
     mean = torch.empty(rows, device=x2d.device)
     rstd = torch.empty(rows, device=x2d.device)
+    if sel is not None:
+        _lib.call("b2p_layernorm_fwd16_sel", _p(x2d), _p(g), _p(b), _p(y), _p(y16), _p(mean), _p(rstd), rows, cols,
+                  float(eps), float(drop_p), seed, _p(sel[0]), _p(sel[1]), _p(sel[2]), _st())
+        return y, y16, mean, rstd
     _lib.call("b2p_layernorm_fwd16", _p(x2d), _p(g), _p(b), _p(y), _p(y16), _p(mean), _p(rstd), rows, cols,
               float(eps), float(drop_p), seed, _st())
     return y, y16, mean, rstd
 
 
 def _ln_bwd16(dy, x, g, mean, rstd, need_params=True, dx_accum=None, drop_p=0.0, seed=0, in_drop_p=-1.0,
-              in_seed=0, dbias_in=None, dx_accum2=None, lazy=None):
+              in_seed=0, dbias_in=None, dx_accum2=None, lazy=None, dy_gate=None, acc2_gate=None):
     """as _ln_bwd, plus d16 = bf16(dx_dropped if in_drop_p >= 0 else dx) (lazy: a sixth entry, the
-    dropout-input bias gradient)"""
+    dropout-input bias gradient). LayerDrop's route folded in: a closed dy_gate stands for dy = 0, and
+    under acc2_gate dx_accum2 is added only when that gate is closed (b2p_layernorm_bwd_gated)."""
     rows, cols = x.shape
     lz = _ln_lazy(lazy, need_params, dbias_in)
     dx = torch.empty_like(x)
@@ -1422,9 +1440,14 @@ def _ln_bwd16(dy, x, g, mean, rstd, need_params=True, dx_accum=None, drop_p=0.0,
     ws = torch.empty(int(_lib.load().b2p_layernorm_bwd_workspace(rows, cols)), device=x.device)
     dxd = torch.empty_like(x) if in_drop_p >= 0.0 else None
     d16 = torch.empty(rows, cols, device=x.device, dtype=BF16)
-    _lib.call("b2p_layernorm_bwd_acc2", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
-              cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, _p(dxd), float(max(in_drop_p, 0.0)), in_seed,
-              None if lz else _p(dbias_in), _p(d16), _p(ws), _st())
+    if dy_gate is not None or acc2_gate is not None:
+        _lib.call("b2p_layernorm_bwd_gated", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
+                  cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, _p(dxd), float(max(in_drop_p, 0.0)),
+                  in_seed, None if lz else _p(dbias_in), _p(d16), _p(dy_gate), _p(acc2_gate), _p(ws), _st())
+    else:
+        _lib.call("b2p_layernorm_bwd_acc2", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
+                  cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, _p(dxd), float(max(in_drop_p, 0.0)),
+                  in_seed, None if lz else _p(dbias_in), _p(d16), _p(ws), _st())
     if lz:
         dg, db = _ln_parts(ws, rows, cols, 0), _ln_parts(ws, rows, cols, 1)
         dbias_in = _ln_parts(ws, rows, cols, 2) if dbias_in is not None else None
@@ -1947,26 +1970,41 @@ class _SkipSlot:
     LayerNorm backward, b2p_layernorm_bwd_acc2, instead of autograd adding the two gradients in a
     separate pass). Exactly one of the two is nonzero (the route kernel writes dout to one side and
     zeros to the other; a skipped layer's gated backward yields exact zeros), so the sum is bitwise the
-    one autograd formed."""
-    __slots__ = ("claimed", "grad")
+    one autograd formed. With a fusing layer form (_LD_FUSE) no route kernel runs: grad is the select's
+    dout itself and the LayerNorm backward adds it only under a closed gate (when_closed)."""
+    __slots__ = ("claimed", "grad", "gate", "fuse", "folded", "when_closed")
 
-    def __init__(self):
+    def __init__(self, gate=None):
         self.claimed = False
         self.grad = None
+        self.gate = gate           # the layer's device flag (layerdrop_layer)
+        self.fuse = False          # the claiming Function folds the select and the route (_LD_FUSE)
+        self.folded = None         # data_ptrs of the output whose last LayerNorm made the select (_ld_folded)
+        self.when_closed = False   # grad is the whole dout: to be added only under a closed gate
 
 
 _SKIP_CLAIM: dict = {}   # data_ptr of a layer input -> its _SkipSlot, while that layer's forward runs
 # False (tests): the skip gradient goes back through autograd (its own add kernel), as before
 _LD_SKIP_FOLD = True
+# LayerDrop's launches folded into the layer's own kernels: the forward select into the layer's last
+# LayerNorm, the backward route into its first and last LayerNorm backward (no ld_select_k / ld_route_k
+# launch), and one flag launch per encoder forward (layerdrop_draws). False (tests): the separate
+# launches, as before. A layer form takes part by claiming its slot with fuse=True (_skip_claim): the
+# post-LN layers (_EncoderLayer16, both forward forms, and the fp32 _EncoderLayer); every other form
+# (stable-LN, Conformer) keeps the launches.
+_LD_FUSE = True
 
 
-def _skip_claim(x):
+def _skip_claim(x, fuse=False):
     """Called by a layer Function's forward with its input: the slot whose skip gradient its backward
-    must add to dx (None when x is not a LayerDrop-selected layer's input or was claimed already)."""
+    must add to dx (None when x is not a LayerDrop-selected layer's input or was claimed already).
+    fuse: this form also makes the select in its last LayerNorm (_ld_sel / _ld_folded) and reads the
+    route from the gate in its backward (_skip_gate)."""
     slot = _SKIP_CLAIM.get(x.data_ptr()) if _SKIP_CLAIM else None
     if slot is None or slot.claimed:
         return None
     slot.claimed = True
+    slot.fuse = bool(fuse and _LD_FUSE and slot.gate is not None and slot.gate is _state.gate)
     return slot
 
 
@@ -1978,10 +2016,37 @@ def _skip_take(slot):
     return g
 
 
+def _ld_sel(slot, x, half=None):
+    """The skip sources of a fusing layer's last LayerNorm: (gate, x, its bf16 image) or, with half (the
+    forward_f16 form: y16 fp16, y16b bf16), (gate, x, its fp16 image, its bf16 image); the images as
+    _LayerDropSelect hands them to ld_select_k (None: packed from x). None when the form does not fuse."""
+    if slot is None or not slot.fuse:
+        return None
+    if half:
+        return (slot.gate, x, _h16_of(x), _b16_of(x))
+    return (slot.gate, x, _b16_of(x))
+
+
+def _ld_folded(slot, res, res16=None, resh=None):
+    """Records the output a fusing layer's last LayerNorm selected into: _LayerDropSelect launches nothing
+    when it is handed exactly this tensor and these 16-bit images (None: the form writes none)."""
+    if slot is not None and slot.fuse:
+        slot.folded = (_p(res), _p(res16), _p(resh))
+
+
+def _skip_gate(slot):
+    """A fusing layer's backward: the gate its LayerNorm backwards read the route from, when the select's
+    backward launched no route kernel. The layer's incoming dy and its slot's gradient are then both the
+    select's whole dout: dy counts as 0 under a closed gate, the slot's gradient is added only under a
+    closed one. None: both arrive routed (or there is no slot) and are used as they are."""
+    return slot.gate if slot is not None and slot.when_closed else None
+
+
 class _LayerDropSelect(torch.autograd.Function):
     """out = keep ? y : x with keep drawn on the device (csrc/layerdrop.hip); the backward routes
     dout to the layer (keep) or around it (skip). With a claimed _SkipSlot the skip gradient goes to
-    the layer's input Function instead of back through autograd."""
+    the layer's input Function instead of back through autograd. When the layer made the select in its
+    own last LayerNorm (slot.folded) this node only wires the gradient: no launch in either direction."""
 
     @staticmethod
     def forward(ctx, x, y, p, seed, slot=None):
@@ -1993,7 +2058,8 @@ class _LayerDropSelect(torch.autograd.Function):
         x16, y16 = (_b16_of(x), _b16_of(y)) if b16 else (None, None)
         # the fp16 copy too when the layer made one (post-LN forward_f16): the next layer reads it uncast
         yh = _h16_of(y) if b16 else None
-        if not b16 or y16 is not None:
+        inplace = not b16 or y16 is not None
+        if inplace:
             # in place: the output is a fresh tensor over y's storage (and y's 16-bit copies), overwritten
             # by x only when the replay's draw skips the layer, so a kept layer's select moves no bytes.
             # Nothing reads y's old values after a skip: the layer's own backward is gated off then.
@@ -2004,8 +2070,14 @@ class _LayerDropSelect(torch.autograd.Function):
             out = torch.empty_like(y)
             out16 = torch.empty(y.shape, device=y.device, dtype=BF16) if b16 else None
             outh = torch.empty(y.shape, device=y.device, dtype=torch.float16) if yh is not None else None
-        _lib.call("b2p_layerdrop_select_h", _p(x), _p(y), _p(out), _p(x16), _p(y16), _p(out16),
-                  _p(_h16_of(x)) if outh is not None else None, _p(yh), _p(outh), y.numel(), float(p), seed, _st())
+        # the layer's last LayerNorm made this select already (_ld_folded): nothing to launch, here or in
+        # the backward
+        ctx.folded = (slot is not None and slot.folded is not None and inplace and
+                      slot.folded == (_p(y), _p(y16), _p(yh)))
+        if not ctx.folded:
+            _lib.call("b2p_layerdrop_select_h", _p(x), _p(y), _p(out), _p(x16), _p(y16), _p(out16),
+                      _p(_h16_of(x)) if outh is not None else None, _p(yh), _p(outh), y.numel(), float(p), seed,
+                      _st())
         ctx.p, ctx.seed, ctx.slot = p, seed, slot
         if out16 is not None:
             attach16(out, out16)
@@ -2016,6 +2088,13 @@ class _LayerDropSelect(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         dout = dout.contiguous()
+        if ctx.folded:
+            # no route: the layer and the slot both get dout itself (nothing writes into it), and the
+            # layer's LayerNorm backwards read the draw (_skip_gate)
+            ctx.slot.grad, ctx.slot.when_closed = dout, True
+            return None, dout, None, None, None
+        if ctx.slot is not None:
+            ctx.slot.when_closed = False
         d_keep = torch.empty_like(dout)
         d_skip = torch.empty_like(dout)
         _lib.call("b2p_layerdrop_route", _p(dout), _p(d_keep), _p(d_skip), dout.numel(), float(ctx.p), ctx.seed, _st())
@@ -2045,14 +2124,38 @@ def layerdrop_param_gates() -> dict:
     return {k: f for k, (r, f) in _LD_PARAM_GATE.items() if r() is not None}
 
 
-def layerdrop_layer(layer, x, p):
+def layerdrop_draws(n, p, device):
+    """The draws of an encoder forward's n layers, made up front: [(seed, flag)] in layer order, the seeds
+    from LD_SEEDS as layerdrop_layer draws them one by one, the flags as views of one int32 buffer that
+    one launch fills (b2p_layerdrop_flags) instead of one launch per layer. Each entry is layerdrop_layer's
+    `drawn`. None (every layer then draws and launches for itself) with _LD_FUSE off."""
+    if not _LD_FUSE or n <= 0:
+        return None
+    seeds = [LD_SEEDS.next() for _ in range(n)]
+    if LAYERDROP_LOG is not None:
+        LAYERDROP_LOG.extend(seeds)
+    flags = torch.empty(n, dtype=torch.int32, device=device)
+    _lib.call("b2p_layerdrop_flags", _p(flags), (ctypes.c_uint64 * n)(*seeds), n, float(p), _st())
+    return [(s, flags[i:i + 1]) for i, s in enumerate(seeds)]
+
+
+def layerdrop_layer(layer, x, p, drawn=None):
     """One encoder layer under LayerDrop inside a captured step (see csrc/layerdrop.hip): the layer
     always runs, its output or its input is selected by the device draw of this replay, and float
     buffers it updates in place (Conformer BatchNorm running statistics) are restored when it is
-    skipped. Eager steps keep the reference's host draw and skip the layer outright."""
+    skipped. Eager steps keep the reference's host draw and skip the layer outright.
+    drawn: this layer's (seed, flag) of layerdrop_draws; None draws the seed and launches the flag here."""
+    if drawn is not None:
+        return _layerdrop_layer(layer, x, p, drawn[0], drawn[1])
     seed = LD_SEEDS.next()
     if LAYERDROP_LOG is not None:
         LAYERDROP_LOG.append(seed)
+    flag = torch.empty(1, dtype=torch.int32, device=x.device)
+    _lib.call("b2p_layerdrop_flag", _p(flag), float(p), seed, _st())
+    return _layerdrop_layer(layer, x, p, seed, flag)
+
+
+def _layerdrop_layer(layer, x, p, seed, flag):
     bufs = [b for b in layer.buffers() if b.is_floating_point() and b.numel() % 4 == 0]
     # BatchNorm running statistics are updated by bn_finalize_k, which reads the gate itself and
     # leaves them untouched in a replay that skips the layer: no snapshot / restore launches
@@ -2061,14 +2164,12 @@ def layerdrop_layer(layer, x, p):
     bufs = [b for b in bufs if id(b) not in bn]
     olds = [b.clone() for b in bufs]
     y = None
-    flag = torch.empty(1, dtype=torch.int32, device=x.device)
     _GATE_FLAGS.append(flag)      # referenced by the captured graph's kernels: kept for its life
-    _lib.call("b2p_layerdrop_flag", _p(flag), float(p), seed, _st())
     for prm in layer.parameters():
         _LD_PARAM_GATE[id(prm)] = (weakref.ref(prm), flag)
     slot = None
     if _LD_SKIP_FOLD and x.requires_grad and x.is_contiguous():
-        slot = _SkipSlot()
+        slot = _SkipSlot(flag)
         _SKIP_CLAIM[x.data_ptr()] = slot
     try:
         # the layer's GEMMs and fused attention (forward, backward, deferred weight gradients) read
@@ -2451,7 +2552,8 @@ def _attn16_bwd(qkv16, dO16, lse2, B, T, nh, dh, p_attn, seed, want32=True, mask
 class _EncoderLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg, wq, bq, wk, bk, wv, bv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2):
-        ctx.skip = _skip_claim(x)   # LayerDrop skip gradient folded into dx (_SkipSlot)
+        # LayerDrop skip gradient folded into dx (_SkipSlot); this form also folds the select and the route
+        ctx.skip = _skip_claim(x, fuse=True)
         nh, eps, p_attn, p_hid, p_act, seeds = cfg
         _chk(x, "encoder_layer.x")
         B, T, D = x.shape
@@ -2477,12 +2579,14 @@ class _EncoderLayer(torch.autograd.Function):
         y2 = torch.empty(NT, D, device=dev)
         gemm(NT, D, F, op(f, 0, F, True), op(w2, 0, F, True), y2, D, bias=b2, drop_p=p_hid, seed=seeds[3],
              residual=x1)
-        out, m2, r2 = _ln_fwd(y2, g2, be2, eps)
+        out, m2, r2 = _ln_fwd(y2, g2, be2, eps, sel=_ld_sel(ctx.skip, x))
         ctx.save_for_backward(x, qkv, P, Pd, O, y1, x1, m1, r1, pre, f, y2, m2, r2,
                               wq, wk, wv, wo, g1, w1, w2, g2)
         ctx.cfg = cfg
         ctx.has_b = [b is not None for b in (bq, bk, bv, bo, b1, b2)]
-        return out.view(B, T, D)
+        res = out.view(B, T, D)
+        _ld_folded(ctx.skip, res)
+        return res
 
     @staticmethod
     def backward(ctx, dout):
@@ -2498,9 +2602,11 @@ class _EncoderLayer(torch.autograd.Function):
         ng = ctx.needs_input_grad
         dout = dout.contiguous().view(NT, D)
         x2 = x.view(NT, D)
+        ld_gate = _skip_gate(ctx.skip)   # LayerDrop route folded in, as in _EncoderLayer16.backward
         # LN2 backward -> dy2 ; dz2 = dropout-mask(dy2) (output dropout of the FFN)
         db2 = torch.empty(D, device=dev) if ng[15] else None
-        dy2, dg2, dbe2, dz2 = _ln_bwd(dout, y2, g2, m2, r2, True, in_drop_p=p_hid, in_seed=seeds[3], dbias_in=db2)
+        dy2, dg2, dbe2, dz2 = _ln_bwd(dout, y2, g2, m2, r2, True, in_drop_p=p_hid, in_seed=seeds[3], dbias_in=db2,
+                                      dy_gate=ld_gate)
         dw2 = torch.empty_like(w2) if ng[14] else None
         if dw2 is not None:
             mm_tn(dz2, f, dw2)
@@ -2521,7 +2627,7 @@ class _EncoderLayer(torch.autograd.Function):
         # LN1 backward -> dy1 ; dz1 = dropout-mask(dy1) (attention output dropout)
         dbo = torch.empty(D, device=dev) if ng[9] else None
         dy1, dg1, dbe1, dz1 = _ln_bwd(dx1, y1, g1, m1, r1, True, in_drop_p=p_hid, in_seed=seeds[1], dbias_in=dbo,
-                                       dx_accum2=_skip_take(ctx.skip))
+                                       dx_accum2=_skip_take(ctx.skip), acc2_gate=ld_gate)
         dwo = torch.empty_like(wo) if ng[8] else None
         if dwo is not None:
             mm_tn(dz1, O, dwo)
@@ -2557,7 +2663,8 @@ class _EncoderLayer16(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cfg, wq, bq, wk, bk, wv, bv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2):
-        ctx.skip = _skip_claim(x)   # LayerDrop skip gradient folded into dx (_SkipSlot)
+        # LayerDrop skip gradient folded into dx (_SkipSlot); this form also folds the select and the route
+        ctx.skip = _skip_claim(x, fuse=True)
         nh, eps, p_attn, p_hid, p_act, seeds = cfg
         _chk(x, "encoder_layer.x")
         B, T, D = x.shape
@@ -2603,7 +2710,7 @@ class _EncoderLayer16(torch.autograd.Function):
         gemm(NT, D, F, op(f16, 0, F, True), op(w2_16, 0, F, True), y2, D, bias=b2, drop_p=p_hid, seed=seeds[3],
              residual=x1)
         del x1
-        out, out16, m2, r2 = _ln_fwd16(y2, g2, be2, eps)
+        out, out16, m2, r2 = _ln_fwd16(y2, g2, be2, eps, sel=_ld_sel(ctx.skip, x))
         ctx.save_for_backward(x16, qkv, P, Pd, O16, y1, x1_16, m1, r1, pre, f16, y2, m2, r2,
                               wq, wk, wv, wo, g1, w1, w2, g2)
         ctx.cfg = cfg
@@ -2613,6 +2720,7 @@ class _EncoderLayer16(torch.autograd.Function):
         ctx.has_b = [b is not None for b in (bq, bk, bv, bo, b1, b2)]
         res = out.view(B, T, D)
         attach16(res, out16.view(B, T, D))
+        _ld_folded(ctx.skip, res, out16)
         return res
 
     @staticmethod
@@ -2647,7 +2755,8 @@ class _EncoderLayer16(torch.autograd.Function):
         gemm(NT, D, F, op(fh, 0, F, True), op(weight16(w2, half=True), 0, F, True), y2, D, bias=b2, drop_p=p_hid,
              seed=seeds[3], residual=x1)
         del x1, fh
-        out, outh, m2, r2, out16 = _ln_fwd_x16(y2, g2, be2, eps, True, want32=True, want_b16=True)
+        out, outh, m2, r2, out16 = _ln_fwd_x16(y2, g2, be2, eps, True, want32=True, want_b16=True,
+                                               sel=_ld_sel(ctx.skip, x, half=True))
         ctx.save_for_backward(x16, qkv, P, Pd, O16, y1, x1_16, m1, r1, pre, f16, y2, m2, r2,
                               wq, wk, wv, wo, g1, w1, w2, g2)
         ctx.cfg = cfg
@@ -2658,12 +2767,16 @@ class _EncoderLayer16(torch.autograd.Function):
         res = out.view(B, T, D)
         attach16(res, out16.view(B, T, D))
         attach16h(res, outh.view(B, T, D))
+        _ld_folded(ctx.skip, res, out16, outh)
         return res
 
     @staticmethod
     def backward(ctx, dout):
         (x16, qkv, P, Pd, O16, y1, x1_16, m1, r1, pre, f16, y2, m2, r2, wq, wk, wv, wo, g1, w1, w2,
          g2) = ctx.saved_tensors
+        # LayerDrop route folded in: dout is the select's whole dout (shared with the slot: only read
+        # here), 0 under a closed gate for LN2's backward, the skip gradient under one for LN1's
+        ld_gate = _skip_gate(ctx.skip)
         nh, eps, p_attn, p_hid, p_act, seeds = ctx.cfg
         B, T, D = ctx.shape
         dh = D // nh
@@ -2678,7 +2791,8 @@ class _EncoderLayer16(torch.autograd.Function):
         db2 = torch.empty(D, device=dev) if ng[15] else None
         prm = ctx.prm
         dy2, dg2, dbe2, _dz2, dz2_16, db2 = _ln_bwd16(dout, y2, g2, m2, r2, True, in_drop_p=p_hid, in_seed=seeds[3],
-                                                      dbias_in=db2, lazy=(prm[14], prm[15], prm[13] if ng[15] else None))
+                                                      dbias_in=db2, lazy=(prm[14], prm[15], prm[13] if ng[15] else None),
+                                                      dy_gate=ld_gate)
         del _dz2
         dw2 = None
         if ng[14]:
@@ -2709,7 +2823,8 @@ class _EncoderLayer16(torch.autograd.Function):
         dbo = torch.empty(D, device=dev) if ng[9] else None
         dy1, dg1, dbe1, _dz1, dz1_16, dbo = _ln_bwd16(dx1, y1, g1, m1, r1, True, in_drop_p=p_hid, in_seed=seeds[1],
                                                       dbias_in=dbo, dx_accum2=_skip_take(ctx.skip),
-                                                      lazy=(prm[8], prm[9], prm[7] if ng[9] else None))
+                                                      lazy=(prm[8], prm[9], prm[7] if ng[9] else None),
+                                                      acc2_gate=ld_gate)
         del _dz1
         dwo = None
         if ng[8]:
@@ -2981,17 +3096,23 @@ def _drop_cast_colsum(dy, p, seed, scale, want_colsum, lazy=False):
     return y16, (ColsumParts(parts) if lazy else colsum_from_parts(parts, torch.empty(N, device=dy.device)))
 
 
-def _ln_fwd_x16(x2d, g, b, eps, half, want32=True, want_b16=False):
+def _ln_fwd_x16(x2d, g, b, eps, half, want32=True, want_b16=False, sel=None):
     """LayerNorm (fp32 y unless want32=False, mean, rstd) plus its 16-bit GEMM operand copy (fp16 when
-    half) in one pass; want_b16 adds a bf16 copy (the backward's weight-gradient operand) as a 5th value."""
+    half) in one pass; want_b16 adds a bf16 copy (the backward's weight-gradient operand) as a 5th value.
+    sel (LayerDrop's forward select folded in, _ld_sel): (gate, skip, skip16 or None, skip16b or None), the
+    sources y / y16 / y16b receive under a closed gate."""
     rows, cols = x2d.shape
     y = torch.empty_like(x2d) if want32 else None
     y16 = torch.empty(rows, cols, device=x2d.device, dtype=torch.float16 if half else BF16)
     y16b = torch.empty(rows, cols, device=x2d.device, dtype=BF16) if want_b16 else None
     mean = torch.empty(rows, device=x2d.device)
     rstd = torch.empty(rows, device=x2d.device)
-    _lib.call("b2p_layernorm_fwd_x16", _p(x2d), _p(g), _p(b), _p(y), _p(y16), int(half), _p(y16b), _p(mean),
-              _p(rstd), rows, cols, float(eps), _st())
+    if sel is not None:
+        _lib.call("b2p_layernorm_fwd_x16_sel", _p(x2d), _p(g), _p(b), _p(y), _p(y16), int(half), _p(y16b), _p(mean),
+                  _p(rstd), rows, cols, float(eps), _p(sel[0]), _p(sel[1]), _p(sel[2]), _p(sel[3]), _st())
+    else:
+        _lib.call("b2p_layernorm_fwd_x16", _p(x2d), _p(g), _p(b), _p(y), _p(y16), int(half), _p(y16b), _p(mean),
+                  _p(rstd), rows, cols, float(eps), _st())
     if want_b16:
         return y, y16, mean, rstd, y16b
     return y, y16, mean, rstd

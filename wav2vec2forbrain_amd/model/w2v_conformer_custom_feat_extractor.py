@@ -116,10 +116,11 @@ class Wav2Vec2ConformerEncoder(nn.Module):
         c = self.config
         hidden_states = Fn.dropout(hidden_states, c.hidden_dropout, self.training)
         graph_ld = self.training and c.layerdrop > 0 and Fn.capturing()
-        for layer in self.layers:
+        drawn = Fn.layerdrop_draws(len(self.layers), c.layerdrop, hidden_states.device) if graph_ld else None
+        for k, layer in enumerate(self.layers):
             dropout_probability = torch.rand([])
             if graph_ld:   # captured step: device-drawn LayerDrop (Fn.layerdrop_layer)
-                hidden_states = Fn.layerdrop_layer(layer, hidden_states, c.layerdrop)
+                hidden_states = Fn.layerdrop_layer(layer, hidden_states, c.layerdrop, drawn and drawn[k])
                 continue
             skip = self.training and bool(dropout_probability < c.layerdrop)
             if not skip:

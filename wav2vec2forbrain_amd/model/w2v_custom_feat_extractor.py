@@ -124,12 +124,14 @@ class Wav2Vec2Encoder(nn.Module):
         hidden_states = Fn.pos_conv_ln(hidden_states, g, v, cb, self.layer_norm.weight, self.layer_norm.bias,
                                        self.pos_conv_embed.groups, c.layer_norm_eps, c.hidden_dropout, self.training)
         graph_ld = self.training and c.layerdrop > 0 and Fn.capturing()
-        for layer in self.layers:
+        # the device draws of all layers up front: one flag launch (None: one per layer)
+        drawn = Fn.layerdrop_draws(len(self.layers), c.layerdrop, hidden_states.device) if graph_ld else None
+        for k, layer in enumerate(self.layers):
             # LayerDrop: one CPU torch.rand([]) draw per layer, as the reference's encoder does; inside
             # a captured step the draw moves to the device (redrawn on every replay)
             dropout_probability = torch.rand([])
             if graph_ld:
-                hidden_states = Fn.layerdrop_layer(layer, hidden_states, c.layerdrop)
+                hidden_states = Fn.layerdrop_layer(layer, hidden_states, c.layerdrop, drawn and drawn[k])
                 continue
             skip_the_layer = self.training and bool(dropout_probability < c.layerdrop)
             if not skip_the_layer:
@@ -153,10 +155,11 @@ class Wav2Vec2EncoderStableLayerNorm(Wav2Vec2Encoder):
         hidden_states = Fn.pos_conv_ln(hidden_states, g, v, cb, None, None, self.pos_conv_embed.groups,
                                        c.layer_norm_eps, c.hidden_dropout, self.training)
         graph_ld = self.training and c.layerdrop > 0 and Fn.capturing()
-        for layer in self.layers:
+        drawn = Fn.layerdrop_draws(len(self.layers), c.layerdrop, hidden_states.device) if graph_ld else None
+        for k, layer in enumerate(self.layers):
             dropout_probability = torch.rand([])
             if graph_ld:
-                hidden_states = Fn.layerdrop_layer(layer, hidden_states, c.layerdrop)
+                hidden_states = Fn.layerdrop_layer(layer, hidden_states, c.layerdrop, drawn and drawn[k])
                 continue
             if not (self.training and bool(dropout_probability < c.layerdrop)):
                 hidden_states = layer(hidden_states)
