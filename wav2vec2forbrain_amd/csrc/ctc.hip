@@ -176,7 +176,7 @@ __global__ void __launch_bounds__(256) ctc_grad_k(const int64_t* __restrict__ ta
                                                   const int64_t* __restrict__ tgt_lens, int B, int T, int S, int C,
                                                   int blank, const float* __restrict__ ws,
                                                   const float* __restrict__ nll_in, float* __restrict__ grad) {
-  __shared__ float acc[4][64];
+  __shared__ float acc[4][64], ref[4][64];
   const int b = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int t = 4 * blockIdx.y + w;
   if (t >= T) return;
@@ -194,32 +194,41 @@ __global__ void __launch_bounds__(256) ctc_grad_k(const int64_t* __restrict__ ta
   }
   const int64_t* tg = targets + (int64_t)b * S;
   float vs[NS];
+  int cls[NS];
   float m = -INFINITY;
 #pragma unroll
   for (int j = 0; j < NS; ++j) {
     const int s = NS * lane + j;
+    cls[j] = s < si.L ? ext_label(tg, s, blank, C) : blank;
     vs[j] = s < si.L ? at[s] + bt[s] : -INFINITY;
     m = fmaxf(m, vs[j]);
   }
   m = warp_max(m);
-  for (int c = lane; c < 64; c += 64) acc[w][c] = 0.f;
+  // Per-class logsumexp of alpha + beta around the frame's maximum m. alpha + beta counts the frame's
+  // log-prob twice, so a class whose log-prob l lies far below the best state's sits that far below m
+  // whatever its posterior: 88 below, it lost its whole posterior to fp32 underflow (one-hot logits 100
+  // apart: the gradient was off by its maximum). Such a class (m + nll - l > 60) is summed around
+  // l - nll instead, where its terms are the state posteriors themselves (<= 1) and their sum is the
+  // class posterior. Every other class keeps m: the same bits as when m was the only reference.
+  const float l = lane < C ? lp[lane] : 0.f;
+  acc[w][lane] = 0.f;
+  const bool far = m + nll - l > 60.f;
+  ref[w][lane] = far ? l - nll : m;
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int j = 0; j < NS; ++j) {
-    const int s = NS * lane + j;
-    if (vs[j] != -INFINITY) atomicAdd(&acc[w][ext_label(tg, s, blank, C)], __expf(vs[j] - m));
-  }
+  for (int j = 0; j < NS; ++j)
+    if (vs[j] != -INFINITY) atomicAdd(&acc[w][cls[j]], __expf(vs[j] - ref[w][cls[j]]));
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const float gscale = 1.0f / ((float)B * (float)(si.tl > 1 ? si.tl : 1));
   // classes c = lane (C <= 64, checked on the host)
   float g = 0.f, e = 0.f;
   if (lane < C) {
-    const float l = lp[lane];
     const float a = acc[w][lane];
     const float lcab = (a > 0.f && m != -INFINITY) ? m + __logf(a) : -INFINITY;
     e = __expf(l);
-    g = (e - (lcab == -INFINITY ? 0.f : __expf(lcab + nll - l))) * gscale;
+    const float post = far ? a : (lcab == -INFINITY ? 0.f : __expf(lcab + nll - l));
+    g = (e - post) * gscale;
   }
   const float gsum = warp_sum(g);
   if (lane < C) gt[lane] = g - e * gsum;
