@@ -353,6 +353,43 @@ int64_t b2p_ctc_beam_workspace(int64_t B, int64_t T, int64_t beam);
 int b2p_ctc_prefix_beam(const float* logits, int64_t B, int64_t T, int64_t C, const int32_t* lens, int64_t beam,
                         int blank, float token_min_logp, float beam_prune_logp, int32_t* workspace,
                         int32_t* out_tokens, int32_t* out_len, float* out_score, b2p_stream_t stream);
+/* The device image of a word-level back-off n-gram LM (wav2vec2forbrain_amd/util/ngram_lm.py builds
+ * it from an ARPA file): two open-addressing hash tables with linear probing, capacities powers of
+ * two, load <= 0.5, key 0 = empty slot. A key is the 64-bit fingerprint of (node, token id) for the
+ * character trie and of the word ids (w1 .. wk) for the n-gram table: a chain of splitmix64
+ * finalisers from the table's seed, which the host verified to be distinct within the table.
+ * node 0 is the root; node_word[node] is the id of the word that ends there or -1; ng_vals holds
+ * (alpha * ln p, alpha * ln back-off) float pairs; bos_id / eos_id are -1 if the LM has no <s> /
+ * </s>. All pointers are device pointers. */
+typedef struct {
+  const uint64_t* trie_keys;
+  const int32_t* trie_child;
+  const int32_t* node_word;
+  const uint64_t* ng_keys;
+  const float* ng_vals;
+  int64_t trie_capacity, ng_capacity;
+  uint64_t trie_seed, ng_seed;
+  int32_t order, unk_id, bos_id, eos_id;
+  float beta;
+  int32_t reserved;
+} b2p_ngram_lm;
+/* CTC prefix beam search with shallow fusion of that LM (csrc/beam_lm.hip; the reference's
+ * pyctcdecode + KenLM test decode, src/train/evaluator.py:189-210). The search is
+ * b2p_ctc_prefix_beam's with rank = (log p_ctc + acc) + pen in place of log p_ctc: acc accumulates
+ * ((sum of back-offs + logp) + unk) + beta per word ended by the token delim (unk =
+ * unk_score_scaled = alpha * ln10 * unk_score_offset for a word the LM does not have), pen =
+ * unk_score_offset * max(1, len / 6) while the word part is no prefix of an LM word. At the end a
+ * trailing word part is scored and, with score_boundary, </s> (the history then starts with <s>);
+ * the beam with the best final rank is returned. LM order 1 to 5, beam <= 128, C <= 64, delim !=
+ * blank. workspace: b2p_ctc_beam_lm_workspace(B, T, beam) int32. Outputs: out_tokens (B, T) (-1
+ * padded), out_len (B), out_ctc_logp (B) the prefix's CTC log probability, out_score (B) the fused
+ * score. Parity against pyctcdecode itself is unpinned. */
+int64_t b2p_ctc_beam_lm_workspace(int64_t B, int64_t T, int64_t beam);
+int b2p_ctc_prefix_beam_lm(const float* logits, int64_t B, int64_t T, int64_t C, const int32_t* lens, int64_t beam,
+                           int blank, int delim, float token_min_logp, float beam_prune_logp,
+                           const b2p_ngram_lm* lm, float unk_score_offset, float unk_score_scaled,
+                           int score_boundary, int32_t* workspace, int32_t* out_tokens, int32_t* out_len,
+                           float* out_ctc_logp, float* out_score, b2p_stream_t stream);
 
 /* Grouped positional conv of wav2vec2 on bf16 MFMA (csrc/posconv16.hip; 48 channels per group,
  * 128 taps, padding 64 + SamePad, T <= 256), replacing the implicit-conv GEMMs of

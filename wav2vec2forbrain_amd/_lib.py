@@ -57,6 +57,16 @@ class GemmDesc(ctypes.Structure):
     ]
 
 
+class NgramLM(ctypes.Structure):
+    """b2p_ngram_lm: the device image of an n-gram LM (util/ngram_lm.py)."""
+    _fields_ = [
+        ("trie_keys", c_p), ("trie_child", c_p), ("node_word", c_p), ("ng_keys", c_p), ("ng_vals", c_p),
+        ("trie_capacity", c_i64), ("ng_capacity", c_i64), ("trie_seed", c_u64), ("ng_seed", c_u64),
+        ("order", c_i32), ("unk_id", c_i32), ("bos_id", c_i32), ("eos_id", c_i32), ("beta", c_f32),
+        ("reserved", c_i32),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "b2p_last_error": (ctypes.c_char_p, []),
@@ -140,6 +150,9 @@ _SIGS = {
     "b2p_ctc_greedy_wer": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p]),
     "b2p_ctc_beam_workspace": (c_i64, [c_i64, c_i64, c_i64]),
     "b2p_ctc_prefix_beam": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i32, c_f32, c_f32, c_p, c_p, c_p, c_p, c_p]),
+    "b2p_ctc_beam_lm_workspace": (c_i64, [c_i64, c_i64, c_i64]),
+    "b2p_ctc_prefix_beam_lm": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i32, c_i32, c_f32, c_f32,
+                                       ctypes.POINTER(NgramLM), c_f32, c_f32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     "b2p_ctc_greedy_cer": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p]),
     "b2p_transpose_bf16": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p]),
     "b2p_posconv16_fwd": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p]),

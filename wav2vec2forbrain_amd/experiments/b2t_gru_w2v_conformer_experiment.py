@@ -39,6 +39,10 @@ class B2TGruAndW2VConformerArgsModel(B2TArgsModel, B2P2TBrainFeatureExtractorArg
     lm_decode_alpha: float = 0.5
     lm_decode_beta: float = 0.5
     lm_score_boundary: bool = False
+    # build additions: the n-gram LM of the test decode is a local ARPA file (plain or .gz), fused into the
+    # on-device beam search (csrc/beam_lm.hip); lm_decode_test_predictions needs the path
+    lm_decode_arpa_path: Optional[str] = None
+    lm_decode_unk_score_offset: float = -10.0
     # build addition: synchronised BatchNorm statistics across data-parallel ranks
     sync_batchnorm: bool = True
 
@@ -80,4 +84,5 @@ class B2TGruAndW2VConformerExperiment(B2TExperiment):
             self.tokenizer, mode, self.yaml_config.cache_dir, W2V_CHECKPOINT_TO_PROCESSOR.get(c.wav2vec_checkpoint, ""),
             track_non_test_predictions, c.lm_decode_test_predictions, c.lm_decode_beam_width,
             c.lm_decode_beam_prune_logp, c.lm_decode_token_min_logp, c.lm_decode_alpha, c.lm_decode_beta,
-            c.lm_score_boundary)
+            c.lm_score_boundary, lm_decode_arpa_path=c.lm_decode_arpa_path,
+            lm_decode_unk_score_offset=c.lm_decode_unk_score_offset)

@@ -51,6 +51,10 @@ class B2TGruAndW2VArgsModel(B2TArgsModel, B2P2TBrainFeatureExtractorArgsModel, W
     lm_decode_alpha: float = 0.5
     lm_decode_beta: float = 0.5
     lm_score_boundary: bool = False
+    # build additions: the n-gram LM of the test decode is a local ARPA file (plain or .gz), fused into the
+    # on-device beam search (csrc/beam_lm.hip); lm_decode_test_predictions needs the path
+    lm_decode_arpa_path: Optional[str] = None
+    lm_decode_unk_score_offset: float = -10.0
     store_brain_encoder: bool = Field(default=False, description=(
         "Store brain encoder model seperate from whole model in results directory"))
 
@@ -119,7 +123,8 @@ class B2TGruAndW2VExperiment(B2TExperiment):
             self.tokenizer, mode, self.yaml_config.cache_dir, W2V_CHECKPOINT_TO_PROCESSOR.get(c.wav2vec_checkpoint, ""),
             track_non_test_predictions, c.lm_decode_test_predictions, c.lm_decode_beam_width,
             c.lm_decode_beam_prune_logp, c.lm_decode_token_min_logp, c.lm_decode_alpha, c.lm_decode_beta,
-            c.lm_score_boundary)
+            c.lm_score_boundary, lm_decode_arpa_path=c.lm_decode_arpa_path,
+            lm_decode_unk_score_offset=c.lm_decode_unk_score_offset)
 
     def store_trained_model(self, trained_model: W2VBrainEncoderModel):
         super().store_trained_model(trained_model)

@@ -3005,6 +3005,42 @@ def ctc_prefix_beam(logits, lens=None, beam=100, blank=0, token_min_logp=-5.0, b
     return tok, n, score
 
 
+def ctc_prefix_beam_lm(logits, lens, lm, beam=100, blank=0, delim=4, token_min_logp=-5.0, beam_prune_logp=-10.0,
+                       unk_score_offset=-10.0, score_boundary=False):
+    """CTC prefix beam search with shallow fusion of a word-level n-gram LM on the device
+    (csrc/beam_lm.hip): the reference's pyctcdecode + KenLM test decode (src/train/evaluator.py:
+    189-210) with the LM read from a local ARPA file. lm is a util.ngram_lm.DeviceNgramLM (it carries
+    alpha, folded into its values, and beta); delim is the word delimiter's token id. Candidates are
+    ranked by (log p_ctc + LM score) + partial-word penalty; the rule is stated in csrc/beam_lm.hip
+    and DESIGN.md; parity against pyctcdecode itself is unpinned. Returns (tokens (B, T) int32, -1
+    padded; lengths (B,) int32; CTC log probabilities (B,) of the returned prefixes; fused scores
+    (B,))."""
+    from .util.ngram_lm import scale32
+    _chk(logits, "ctc_prefix_beam_lm.logits")
+    B, T, C = logits.shape
+    dev = logits.device
+    if lm.device != dev:
+        raise ValueError(f"ctc_prefix_beam_lm: the LM image is on {lm.device}, the logits on {dev}")
+    if (lm.image.blank, lm.image.delim) != (blank, delim):
+        raise ValueError(f"ctc_prefix_beam_lm: the LM image was built for blank {lm.image.blank} / delimiter "
+                         f"{lm.image.delim}, not {blank} / {delim}")
+    lens32 = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    ws = torch.empty(int(_lib.load().b2p_ctc_beam_lm_workspace(B, T, beam)), device=dev, dtype=torch.int32)
+    tok = torch.empty(B, T, device=dev, dtype=torch.int32)
+    n = torch.empty(B, device=dev, dtype=torch.int32)
+    ctc = torch.empty(B, device=dev)
+    score = torch.empty(B, device=dev)
+    im = lm.image
+    desc = _lib.NgramLM(_p(lm.trie_keys), _p(lm.trie_child), _p(lm.node_word), _p(lm.ng_keys), _p(lm.ng_vals),
+                        lm.trie_keys.numel(), lm.ng_keys.numel(), im.trie_seed, im.ng_seed, im.order, im.unk_id,
+                        im.bos_id, im.eos_id, lm.beta, 0)
+    _lib.call("b2p_ctc_prefix_beam_lm", _p(logits), B, T, C, _p(lens32), beam, blank, delim, float(token_min_logp),
+              float(beam_prune_logp), ctypes.byref(desc), float(unk_score_offset),
+              float(scale32(lm.alpha, unk_score_offset)), int(bool(score_boundary)), _p(ws), _p(tok), _p(n), _p(ctc),
+              _p(score), _st())
+    return tok, n, ctc, score
+
+
 _TOKCHARS: dict = {}
 
 

@@ -8,8 +8,19 @@ ctc_greedy_wer / ctc_greedy_cer) and only the scalars cross to the
 transfer with the loss. Strings are still built on the host where the reference keeps them (test
 mode, track_non_test_predictions), from the same greedy decode.
 
-LM decoding (pyctcdecode + KenLM through Wav2Vec2ProcessorWithLM, src/train/evaluator.py:148-210)
-needs hub/KenLM assets that are not available offline; lm_decode_test_predictions raises.
+LM decoding (pyctcdecode + KenLM through Wav2Vec2ProcessorWithLM, src/train/evaluator.py:148-210):
+the hub's processor and KenLM assets are not available offline, so the n-gram LM is a local ARPA
+file (lm_decode_arpa_path) and the decoder is the on-device LM-fused prefix beam search
+(csrc/beam_lm.hip, functional.ctc_prefix_beam_lm). In test mode it adds word_error_rate_lm_decode and
+char_error_rate_lm_decode and keeps the decoded strings as predictions_lm_decoded. Candidates are
+ranked by (log p_ctc + acc) + pen: acc gains alpha * ln p(word | history) + beta per word ended by
+the delimiter (+ alpha * ln10 * unk_score_offset for a word the LM does not have), pen =
+unk_score_offset * max(1, len / 6) while the word part is no prefix of an LM word; at the end a
+trailing word part is scored and, with lm_score_boundary, </s> after <s> ... . Known differences
+from pyctcdecode: the end-of-sequence score is applied to every beam and not only to beams with a
+trailing word part, no hotwords, no 1e-15 probability clip of the logits; parity against
+pyctcdecode itself is unpinned (it is not installed). Without an ARPA path
+lm_decode_test_predictions raises.
 """
 from __future__ import annotations
 
@@ -158,8 +169,14 @@ class DefaultEvaluator(Evaluator):
         return self.history
 
 
+class EnhancedDecodedBatch(DecodedPredictionBatch):
+    """DecodedPredictionBatch + predictions_lm_decoded, set on the instance (reference :123-124, :210)."""
+    predictions_lm_decoded: list
+
+
 class EvaluatorWithW2vLMDecoder(DefaultEvaluator):
-    """DefaultEvaluator + character error rate (reference :127-242)."""
+    """DefaultEvaluator + character error rate (reference :127-242); in test mode, with
+    lm_decode_test_predictions and lm_decode_arpa_path, the LM-fused beam decode of the module docstring."""
 
     with_cer = True
 
@@ -167,7 +184,8 @@ class EvaluatorWithW2vLMDecoder(DefaultEvaluator):
                  processor_checkpoint: str = "", track_non_test_predictions: bool = False,
                  lm_decode_test_predictions: bool = False, lm_decode_beam_width=None, lm_decode_beam_prune_logp=None,
                  lm_decode_token_min_logp=None, lm_decode_alpha=None, lm_decode_beta=None,
-                 lm_decode_score_boundary=None, beam_decode_test_predictions: bool = False):
+                 lm_decode_score_boundary=None, beam_decode_test_predictions: bool = False,
+                 lm_decode_arpa_path=None, lm_decode_unk_score_offset: float = -10.0):
         super().__init__(tokenizer, mode, track_non_test_predictions)
         # LM-free CTC prefix beam search on the device (csrc/beam.hip) with the LM decode's beam width /
         # pruning: test-mode metrics word/char_error_rate_beam_decode (the LM decode needs hub assets)
@@ -175,12 +193,24 @@ class EvaluatorWithW2vLMDecoder(DefaultEvaluator):
         self.beam_cfg = dict(beam=lm_decode_beam_width or 100,
                              beam_prune_logp=-10.0 if lm_decode_beam_prune_logp is None else lm_decode_beam_prune_logp,
                              token_min_logp=-5.0 if lm_decode_token_min_logp is None else lm_decode_token_min_logp)
+        self.lm_image = None    # the n-gram LM's host image; moved to the device of the first batch
+        self._device_lm = None
         if lm_decode_test_predictions and mode == "test":
-            raise NotImplementedError(
-                f"LM decoding needs Wav2Vec2ProcessorWithLM.from_pretrained({processor_checkpoint!r}) and its KenLM "
-                "model, which are not available offline")
+            if not lm_decode_arpa_path:
+                raise NotImplementedError(
+                    f"LM decoding needs Wav2Vec2ProcessorWithLM.from_pretrained({processor_checkpoint!r}) and its "
+                    "KenLM model, which are not available offline: pass lm_decode_arpa_path, a local ARPA file of "
+                    "the n-gram LM")
+            from ..datasets.tokenizer import vocab_of
+            from ..util.ngram_lm import build_image, read_arpa
+            blank, _, delim = _ids(tokenizer)
+            self.lm_image = build_image(read_arpa(lm_decode_arpa_path), vocab_of(tokenizer), blank, delim)
         self.lm_decode_beam_width = lm_decode_beam_width
-        self.lm_decode_alpha, self.lm_decode_beta = lm_decode_alpha, lm_decode_beta
+        # pyctcdecode's defaults where the reference passes None
+        self.lm_decode_alpha = 0.5 if lm_decode_alpha is None else lm_decode_alpha
+        self.lm_decode_beta = 1.5 if lm_decode_beta is None else lm_decode_beta
+        self.lm_decode_score_boundary = True if lm_decode_score_boundary is None else bool(lm_decode_score_boundary)
+        self.lm_decode_unk_score_offset = lm_decode_unk_score_offset
 
     def beam_decode_predictions(self, predictions: ModelOutput) -> list[str]:
         """Best prefixes of the device beam search as strings (cut after </s>, like the greedy path)."""
@@ -192,10 +222,36 @@ class EvaluatorWithW2vLMDecoder(DefaultEvaluator):
         return [cut_after_eos_token(self.tokenizer.decode(list(tok[b, :n[b]]), group_tokens=False))
                 for b in range(tok.shape[0])]
 
+    def lm_decode_predictions(self, predictions: ModelOutput) -> list[str]:
+        """Best prefixes of the LM-fused device beam search as strings (cut after </s>)."""
+        from .. import functional as Fn
+        from ..util.ngram_lm import DeviceNgramLM
+        logits = predictions.logits.detach().float().contiguous()
+        if self._device_lm is None or self._device_lm.device != logits.device:
+            self._device_lm = DeviceNgramLM(self.lm_image, self.lm_decode_alpha, self.lm_decode_beta, logits.device)
+        blank, _, delim = _ids(self.tokenizer)
+        tok, n, _, _ = Fn.ctc_prefix_beam_lm(logits, predictions.logit_lens, self._device_lm, blank=blank, delim=delim,
+                                             unk_score_offset=self.lm_decode_unk_score_offset,
+                                             score_boundary=self.lm_decode_score_boundary, **self.beam_cfg)
+        tok, n = tok.cpu().numpy(), n.cpu().numpy()
+        return [cut_after_eos_token(self.tokenizer.decode(list(tok[b, :n[b]]), group_tokens=False))
+                for b in range(tok.shape[0])]
+
     def _track_batch(self, predictions: ModelOutput, sample) -> float:
         if self.beam_decode and self.mode == "test" and sample.target is not None and predictions.logits.is_cuda:
             labels = self.tokenizer.batch_decode(sample.target.cpu().numpy(), group_tokens=False)
             pred = self.beam_decode_predictions(predictions)
             predictions.metrics.update({"word_error_rate_beam_decode": word_error_rate(pred, labels),
                                         "char_error_rate_beam_decode": char_error_rate(pred, labels)})
-        return super()._track_batch(predictions, sample)
+        lm_pred = None
+        if self.lm_image is not None and sample.target is not None and predictions.logits.is_cuda:
+            labels = self.tokenizer.batch_decode(sample.target.cpu().numpy(), group_tokens=False)
+            lm_pred = self.lm_decode_predictions(predictions)
+            predictions.metrics.update({"word_error_rate_lm_decode": word_error_rate(lm_pred, labels),
+                                        "char_error_rate_lm_decode": char_error_rate(lm_pred, labels)})
+        loss = super()._track_batch(predictions, sample)
+        if lm_pred is not None and self.history.decoded[-1] is not None:   # strings are kept (test mode)
+            last = self.history.decoded[-1]
+            self.history.decoded[-1] = EnhancedDecodedBatch(last.predictions, last.targets)
+            self.history.decoded[-1].predictions_lm_decoded = lm_pred
+        return loss
