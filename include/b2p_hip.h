@@ -245,6 +245,19 @@ int b2p_layernorm_bwd_gated(const float* dy, const float* x, const float* gamma,
                             uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
                             float* dbias_in, uint16_t* d16, const int32_t* dy_gate, const int32_t* acc2_gate,
                             float* workspace, b2p_stream_t stream);
+/* b2p_layernorm_bwd_gated with a flags word. B2P_LNB_IN_DROP: the dropout-input form (in_drop_p,
+ * in_drop_seed) runs whether or not dx_dropped is given; with dx_dropped = NULL the dropped dx is still
+ * formed, d16 = bf16(dropped dx) and the dbias_in partials / dbias_in are written, only its fp32 image is
+ * not stored (a caller that feeds GEMMs from d16 alone saves rows * cols * 4 bytes of writes). Every
+ * other output is bit for bit that of the call with a dx_dropped destination. flags = 0 is
+ * b2p_layernorm_bwd_gated. */
+#define B2P_LNB_IN_DROP 1u
+int b2p_layernorm_bwd_flags(const float* dy, const float* x, const float* gamma, const float* mean,
+                            const float* rstd, float* dx, float* dgamma, float* dbeta, int64_t rows,
+                            int64_t cols, const float* dx_accum, const float* dx_accum2, float drop_p,
+                            uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
+                            float* dbias_in, uint16_t* d16, const int32_t* dy_gate, const int32_t* acc2_gate,
+                            uint32_t flags, float* workspace, b2p_stream_t stream);
 
 /* fp32 -> bf16 (round to nearest even), the GEMM operand copy of a weight or activation
  * (master copies stay fp32; replaces the implicit .to(bfloat16) of autocast) */
@@ -538,6 +551,22 @@ int b2p_attn16_bwd_f16(const void* qkv16h, const void* dO16, const float* lse2, 
  * accumulate in the same order, so the outputs are bitwise equal. Process-wide; the initial value
  * comes from B2P_ATTN_DKV2 (0 selects the per-tile kernel). */
 int b2p_attn16_dkv_variant(int v);
+/* b2p_attn16_bwd (qkv_fp16 = 0) / b2p_attn16_bwd_f16 (qkv_fp16 = 1) that also leaves the column sums of
+ * the fp32 [dQ | dK | dV] values (the Q / K / V bias gradients) as partial rows, so that a caller whose
+ * GEMMs read dqkv16 needs no fp32 image: dqkv may be NULL (dqkv or dqkv16 must be given).
+ * bias_parts: 3 * P * D floats, D = nh * dh, P = b2p_attn16_bwd_bias_parts_rows(B, T, nh); plane q (0 Q,
+ * 1 K, 2 V) is the contiguous [P][D] block at q * P * D whose rows sum to the column sums of that third
+ * of dqkv (finish them with b2p_colsum_parts or b2p_accum_rows_recs). A row holds the sum, in fp32, over
+ * one 16-row tile of the values stored for it (after the scale multiply, before the bf16 rounding; rows
+ * of the sequence only). Every element is written exactly once per launch without atomics (zeros for a
+ * tile beyond T, and throughout under a closed LayerDrop gate), so the buffer needs no zeroing and the sums repeat
+ * bit for bit; they differ from a column sum of the fp32 image in summation order alone. dqkv, dqkv16
+ * and delta_ws receive the bits of b2p_attn16_bwd[_f16]. */
+int64_t b2p_attn16_bwd_bias_parts_rows(int64_t B, int64_t T, int64_t nh);
+int b2p_attn16_bwd_parts(int qkv_fp16, const void* qkv16, const void* dO16, const float* lse2, float* delta_ws,
+                         float* dqkv, void* dqkv16, float* bias_parts, int64_t B, int64_t T, int64_t nh,
+                         int64_t dh, float scale, float drop_p, uint64_t drop_seed, const uint32_t* mask,
+                         b2p_stream_t stream);
 
 /* ------------------------------------------------------------------ CTC
  * log_softmax + nn.CTCLoss(blank=0, reduction="mean", zero_infinity=True)

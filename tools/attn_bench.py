@@ -1,5 +1,7 @@
 """Times the fused bf16 attention kernels at the bench shape (B=32, T=249, 12 heads x 64).
-usage: python tools/attn_bench.py [B] [T] [nh]"""
+usage: python tools/attn_bench.py [--parts] [B] [T] [nh]
+--parts: also the backward that leaves the Q/K/V bias gradients as per-tile partial sums and writes no fp32
+dqkv image (b2p_attn16_bwd_parts), beside the backward with the image plus the column sum that read it."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,9 +22,11 @@ def timeit(f, n=10):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-T = int(sys.argv[2]) if len(sys.argv) > 2 else 249
-nh = int(sys.argv[3]) if len(sys.argv) > 3 else 12
+PARTS = "--parts" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--parts"]
+B = int(argv[0]) if len(argv) > 0 else 32
+T = int(argv[1]) if len(argv) > 1 else 249
+nh = int(argv[2]) if len(argv) > 2 else 12
 dh = 64
 q = torch.randn(B * T, 3 * nh * dh, device="cuda") * 0.5
 dO = torch.randn(B * T, nh * dh, device="cuda").to(torch.bfloat16)
@@ -41,6 +45,24 @@ for kind in ("f16", "bf16"):
         tb = timeit(lambda: Fn._attn16_bwd(q16, dO, lse2, B, T, nh, dh, p, 5, mask=mask))
         print(f"attn16[{kind}] B={B} T={T} nh={nh} p={p}: fwd {tf:.1f} us ({fl / tf / 1e6:.0f} TFLOP/s), "
               f"bwd {tb:.1f} us ({2.5 * fl / tb / 1e6:.0f} TFLOP/s)", flush=True)
+        if PARTS:
+            D = nh * dh
+            db = torch.empty(3 * D, device="cuda")
+
+            def old():   # fp32 image + the column sum that was its only reader
+                d32, _ = Fn._attn16_bwd(q16, dO, lse2, B, T, nh, dh, p, 5, mask=mask)
+                Fn.colsum(d32, B * T, 3 * D, db)
+
+            def new():   # no image: per-tile partials, finished by one column sum per plane
+                _, _, bp = Fn._attn16_bwd(q16, dO, lse2, B, T, nh, dh, p, 5, want32=False, mask=mask, bias_parts=True)
+                for g in bp:
+                    g.materialize()
+
+            to, tn = timeit(old), timeit(new)
+            tk = timeit(lambda: Fn._attn16_bwd(q16, dO, lse2, B, T, nh, dh, p, 5, want32=False, mask=mask,
+                                               bias_parts=True))
+            print(f"    bias gradients: fp32 image + colsum {to:.1f} us; partials, no image {tk:.1f} us "
+                  f"(+ 3 partial sums: {tn:.1f} us)", flush=True)
 # the bf16 mode's forward with the keep bits drawn ahead (functional.attn_keep_plan: b2p_attn16_keep_masks
 # + b2p_attn16_fwd_f16_keep, DM 3), and the draw itself for one layer
 import ctypes

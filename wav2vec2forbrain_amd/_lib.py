@@ -204,7 +204,13 @@ _SIGS = {
                                           c_p, c_p, c_p]),
     "b2p_layernorm_bwd_gated": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_f32, c_u64,
                                         c_p, c_f32, c_u64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "b2p_layernorm_bwd_flags": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_f32, c_u64,
+                                        c_p, c_f32, c_u64, c_p, c_p, c_p, c_p, c_u32, c_p, c_p]),
+    "b2p_attn16_bwd_bias_parts_rows": (c_i64, [c_i64, c_i64, c_i64]),
+    "b2p_attn16_bwd_parts": (c_i32, [c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f32,
+                                     c_f32, c_u64, c_p, c_p]),
 }
+LNB_IN_DROP = 1    # b2p_layernorm_bwd_flags: the dropout-input form without a dx_dropped image (B2P_LNB_IN_DROP)
 
 # timing families (b2p_timing_*)
 TIMING_GEMM = 1

@@ -142,6 +142,58 @@ __device__ __forceinline__ void zero_block(float* dqkv, uint16_t* dqkv16, int64_
     if (dqkv16) *reinterpret_cast<uint2*>(dqkv16 + o) = make_uint2(0u, 0u);
   }
 }
+// Bias partials (b2p_attn16_bwd_parts): the column sums of the fp32 values a backward kernel stores, held
+// as three planes [3][P][D] (Q | K | V) of P = B * blocks * PART_TILES partial rows, one per 16-row tile:
+// the wave that runs tile j of the workgroup of (b, h, 128-row block blk) owns columns [h*64, h*64 + 64) of
+// row (b * blocks + blk) * PART_TILES + j of its plane(s) and writes them exactly once per launch (zeros
+// for a tile beyond T or under a closed gate), so nothing is zeroed ahead and no atomic is used: the sums
+// repeat bit for bit. A tile's sums are formed at its store from the registers being stored: no register
+// lives across the tile loop for them. PT (compile-time) selects the kernels' forms that do this: the forms
+// without it hold no code or register for it (several dQ forms sit exactly at the 256 registers of two
+// waves per SIMD).
+constexpr int PART_TILES = 8;   // 16-row tiles per 128-row block
+__device__ __forceinline__ float* part_row(float* part, int q, int nblk, int b, int blk, int j, int nh, int h) {
+  const int64_t P = (int64_t)(gridDim.x / nh) * PART_TILES;   // B * blocks * PART_TILES
+  return part + ((int64_t)q * P + ((int64_t)b * nblk + blk) * PART_TILES + j) * (nh * DH) + h * DH;
+}
+// the sum over the 16 lanes of a DPP row (the lanes that share lane >> 4), in every lane: four rotate-adds
+template <int N>
+__device__ __forceinline__ float row_ror(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + N, 0xF, 0xF, false));   // row_ror:N
+}
+__device__ __forceinline__ float row16_sum(float v) {
+  v += row_ror<8>(v);
+  v += row_ror<4>(v);
+  v += row_ror<2>(v);
+  v += row_ror<1>(v);
+  return v;
+}
+// store_out for the lanes with ok (their row lies below T) and, under PT (prow: the tile's partial row, col =
+// this lane's first of four columns in it), the column sums of the stored fp32 values over the tile's 16
+// rows: the product keeps its own rounding (no fused multiply-add into the sum), rows beyond T count as
+// zero. Called by all 64 lanes (the row sum crosses lanes).
+template <bool PT>
+__device__ __forceinline__ void store_out_part(float* o32, uint16_t* o16, int64_t off, const f32x4& v, float s, bool ok,
+                                               float* prow, int col, int lr) {
+  if constexpr (!PT) {
+    if (ok) store_out(o32, o16, off, v, s);
+  } else {
+    float4 f = make_float4(v[0] * s, v[1] * s, v[2] * s, v[3] * s);
+    asm volatile("" : "+v"(f.x), "+v"(f.y), "+v"(f.z), "+v"(f.w));
+    if (ok) {
+      if (o32) *reinterpret_cast<float4*>(o32 + off) = f;
+      if (o16) *reinterpret_cast<uint2*>(o16 + off) = b2p_pack_bf16x4(f);
+    }
+    float4 z;
+    z.x = row16_sum(ok ? f.x : 0.f);
+    z.y = row16_sum(ok ? f.y : 0.f);
+    z.z = row16_sum(ok ? f.z : 0.f);
+    z.w = row16_sum(ok ? f.w : 0.f);
+    if (lr == 0) *reinterpret_cast<float4*>(prow + col) = z;
+  }
+}
+__device__ __forceinline__ void part_zero(float* dst, int l) { dst[l] = 0.f; }
+
 template <bool DROP>
 __device__ __forceinline__ float keep_scale(const DropCfg& dc, uint64_t idx) {
   if (!DROP) return 1.f;
@@ -380,12 +432,12 @@ __global__ void __launch_bounds__(256) attn_keep_k(uint32_t* __restrict__ mask, 
 // bf16) columns [D + h*64, ...) and [2D + h*64, ...). One workgroup per (batch, head, 128 keys): Q and
 // dO are staged once for 128 keys (4 waves x key tiles w and w + 4).
 constexpr int BWD_KB = 128;
-template <int DM, bool H, int TM>   // DM 0: no dropout, 1: hash the keep mask, 2: keep bits in memory; H: fp16 qkv
+template <int DM, bool H, int TM, bool PT = false>   // DM 0: no dropout, 1: hash the keep mask, 2: keep bits in memory; H: fp16 qkv; PT: bias partials
 __global__ void __launch_bounds__(256) attn16_bwd_dkv_k(const uint16_t* __restrict__ qkv, const float* __restrict__ delta,
                                                         const uint16_t* __restrict__ dO16, const float* __restrict__ lse2,
                                                         float* __restrict__ dqkv, uint16_t* __restrict__ dqkv16, int T,
                                                         int nh, float scale, DropCfg dc,
-                                                        const uint32_t* __restrict__ maskw) {
+                                                        const uint32_t* __restrict__ maskw, float* __restrict__ part) {
   static_assert(TM == TMAX || DM != 2, "the stored keep mask covers T <= 256");
   constexpr bool DROP = DM != 0;
   dc.seed = b2p_seed_eff(dc.seed, dc.epoch);
@@ -405,6 +457,12 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv_k(const uint16_t* __restri
       zero_block(dqkv, dqkv16, row0, kb * BWD_KB + 64 * half, T, ld, D + h * DH, tid);
       zero_block(dqkv, dqkv16, row0, kb * BWD_KB + 64 * half, T, ld, 2 * D + h * DH, tid);
     }
+    if constexpr (PT) {
+      for (int j = w; j < BWD_KB / 16; j += 4) {
+        part_zero(part_row(part, 1, nkb, b, kb, j, nh, h), l);
+        part_zero(part_row(part, 2, nkb, b, kb, j, nh, h), l);
+      }
+    }
     return;
   }
   load_image<TM>(smem, qkv, row0, T, ld, h * DH, tid);
@@ -423,6 +481,13 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv_k(const uint16_t* __restri
   const uint64_t bh = (uint64_t)b * nh + h;
   const int TP = T + (T & 1);
   const int kt0 = kb * (BWD_KB / 16) + w;
+  if constexpr (PT) {   // bias partials of this wave's key tiles beyond T: zeros (the loop below never reaches them)
+    for (int j = w; j < BWD_KB / 16; j += 4) {
+      if ((kb * (BWD_KB / 16) + j) * 16 < T) continue;
+      part_zero(part_row(part, 1, nkb, b, kb, j, nh, h), l);
+      part_zero(part_row(part, 2, nkb, b, kb, j, nh, h), l);
+    }
+  }
   for (int kt = kt0; kt < kt0 + BWD_KB / 16 && kt * 16 < T; kt += 4) {
     uint32_t obase = 0;   // opaque image bases: no hoisting of the unrolled body's LDS addresses
     asm volatile("" : "+v"(obase));
@@ -483,12 +548,15 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv_k(const uint16_t* __restri
         dk[dt] = mfma(to_b16<H>(tr_frag(Qimg, 32 * c + 4 * g, 32 * c + 16 + 4 * g, dt * 16, lr)), bs, dk[dt]);
       }
     }
-    if (kok) {
+    {
       const int64_t r = (row0 + key) * ld + h * DH;
+      const int j = kt - kb * (BWD_KB / 16);
+      float* pk = PT ? part_row(part, 1, nkb, b, kb, j, nh, h) : nullptr;
+      float* pv = PT ? part_row(part, 2, nkb, b, kb, j, nh, h) : nullptr;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        store_out(dqkv, dqkv16, r + D + dt * 16 + 4 * g, dk[dt], scale);
-        store_out(dqkv, dqkv16, r + 2 * D + dt * 16 + 4 * g, dv[dt], 1.f);
+        store_out_part<PT>(dqkv, dqkv16, r + D + dt * 16 + 4 * g, dk[dt], scale, kok, pk, dt * 16 + 4 * g, lr);
+        store_out_part<PT>(dqkv, dqkv16, r + 2 * D + dt * 16 + 4 * g, dv[dt], 1.f, kok, pv, dt * 16 + 4 * g, lr);
       }
     }
   }
@@ -502,12 +570,12 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv_k(const uint16_t* __restri
 // are one 16-byte read; validity and keep are all-ones / zero bit masks. Accumulation order per tile
 // is the per-tile kernel's, so both forms write bitwise-equal dK / dV.
 constexpr int MSK_LD = TMAX + 8;
-template <int DM, bool H, int TM>
+template <int DM, bool H, int TM, bool PT = false>
 __global__ void __launch_bounds__(256) attn16_bwd_dkv2_k(const uint16_t* __restrict__ qkv, const float* __restrict__ delta,
                                                          const uint16_t* __restrict__ dO16, const float* __restrict__ lse2,
                                                          float* __restrict__ dqkv, uint16_t* __restrict__ dqkv16, int T,
                                                          int nh, float scale, DropCfg dc,
-                                                         const uint32_t* __restrict__ maskw) {
+                                                         const uint32_t* __restrict__ maskw, float* __restrict__ part) {
   static_assert(TM == TMAX || DM != 2, "the stored keep mask covers T <= 256");
   constexpr bool DROP = DM != 0;
   dc.seed = b2p_seed_eff(dc.seed, dc.epoch);
@@ -527,6 +595,12 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv2_k(const uint16_t* __restr
       zero_block(dqkv, dqkv16, row0, kb * BWD_KB + 64 * half, T, ld, D + h * DH, tid);
       zero_block(dqkv, dqkv16, row0, kb * BWD_KB + 64 * half, T, ld, 2 * D + h * DH, tid);
     }
+    if constexpr (PT) {
+      for (int j = w; j < BWD_KB / 16; j += 4) {
+        part_zero(part_row(part, 1, nkb, b, kb, j, nh, h), l);
+        part_zero(part_row(part, 2, nkb, b, kb, j, nh, h), l);
+      }
+    }
     return;
   }
   load_image<TM>(smem, qkv, row0, T, ld, h * DH, tid);
@@ -542,7 +616,15 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv2_k(const uint16_t* __restr
   }
   __syncthreads();
   const int kt0 = kb * (BWD_KB / 16) + w;
-  if (kt0 * 16 >= T) return;   // both of this wave's key tiles lie beyond T (no barrier follows)
+  if (kt0 * 16 >= T) {   // both of this wave's key tiles lie beyond T (no barrier follows): zero partials
+    if constexpr (PT) {
+      for (int j = w; j < BWD_KB / 16; j += 4) {
+        part_zero(part_row(part, 1, nkb, b, kb, j, nh, h), l);
+        part_zero(part_row(part, 2, nkb, b, kb, j, nh, h), l);
+      }
+    }
+    return;
+  }
   const float c2 = scale * LOG2E;
   const uint64_t bh = (uint64_t)b * nh + h;
   const int TP = T + (T & 1);
@@ -640,13 +722,14 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv2_k(const uint16_t* __restr
   }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    if (key[t] < T) {
-      const int64_t r = (row0 + key[t]) * ld + h * DH;
+    // bias partials: a second tile wholly beyond T has no lane with ok, so its row receives zeros
+    const int64_t r = (row0 + key[t]) * ld + h * DH;
+    float* pk = PT ? part_row(part, 1, nkb, b, kb, w + 4 * t, nh, h) : nullptr;
+    float* pv = PT ? part_row(part, 2, nkb, b, kb, w + 4 * t, nh, h) : nullptr;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        store_out(dqkv, dqkv16, r + D + dt * 16 + 4 * g, dk[t][dt], scale);
-        store_out(dqkv, dqkv16, r + 2 * D + dt * 16 + 4 * g, dv[t][dt], 1.f);
-      }
+    for (int dt = 0; dt < 4; ++dt) {
+      store_out_part<PT>(dqkv, dqkv16, r + D + dt * 16 + 4 * g, dk[t][dt], scale, key[t] < T, pk, dt * 16 + 4 * g, lr);
+      store_out_part<PT>(dqkv, dqkv16, r + 2 * D + dt * 16 + 4 * g, dv[t][dt], 1.f, key[t] < T, pv, dt * 16 + 4 * g, lr);
     }
   }
 }
@@ -657,12 +740,12 @@ __global__ void __launch_bounds__(256) attn16_bwd_dkv2_k(const uint16_t* __restr
 // rounding — otherwise the residual feeds a systematic, Q-correlated error into dK. Pass 1 keeps
 // P and dP*keep in registers, pass 2 forms dS and dQ^T += K^T dS^T. One workgroup per (batch, head,
 // 128 queries): K and V staged once, 4 waves x query tiles w and w + 4.
-template <int DM, bool H, int TM, bool T1 = false>   // DM 0: no dropout, 1: hash, 2: keep bits in memory; H: fp16 qkv; T1: T > TM - 16
+template <int DM, bool H, int TM, bool T1 = false, bool PT = false>   // DM 0: no dropout, 1: hash, 2: keep bits in memory; H: fp16 qkv; T1: T > TM - 16; PT: bias partials
 __global__ void __launch_bounds__(256) attn16_bwd_dq_k(const uint16_t* __restrict__ qkv, float* __restrict__ delta,
                                                        const uint16_t* __restrict__ dO16, const float* __restrict__ lse2,
                                                        float* __restrict__ dqkv, uint16_t* __restrict__ dqkv16, int T,
                                                        int nh, float scale, DropCfg dc,
-                                                       const uint32_t* __restrict__ maskw) {
+                                                       const uint32_t* __restrict__ maskw, float* __restrict__ part) {
   constexpr bool DROP = DM != 0;
   dc.seed = b2p_seed_eff(dc.seed, dc.epoch);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -675,6 +758,8 @@ __global__ void __launch_bounds__(256) attn16_bwd_dq_k(const uint16_t* __restric
   const int64_t row0 = (int64_t)b * T;
   if (b2p_gated_off(dc.gate)) {   // LayerDrop: zero dQ (the bias reduction reads it)
     for (int half = 0; half < FWD_QB / 64; ++half) zero_block(dqkv, dqkv16, row0, qh * FWD_QB + 64 * half, T, ld, h * DH, tid);
+    if constexpr (PT)
+      for (int j = w; j < FWD_QB / 16; j += 4) part_zero(part_row(part, 0, nqh, b, qh, j, nh, h), l);
     return;
   }
   static_assert(TM == TMAX || DM != 2, "the stored keep mask covers T <= 256");
@@ -687,6 +772,10 @@ __global__ void __launch_bounds__(256) attn16_bwd_dq_k(const uint16_t* __restric
   uint32_t tailm[4];   // T1: validity masks of this lane's keys in the last key tile
 #pragma unroll
   for (int i = 0; i < 4; ++i) tailm[i] = (uint32_t)((TM - 16 + 4 * g + i - T) >> 31);
+  if constexpr (PT) {   // bias partials of this wave's query tiles beyond T: zeros (the loop below never reaches them)
+    for (int j = w; j < FWD_QB / 16; j += 4)
+      if ((qh * (FWD_QB / 16) + j) * 16 >= T) part_zero(part_row(part, 0, nqh, b, qh, j, nh, h), l);
+  }
   for (int qt = qt0; qt < qt0 + FWD_QB / 16 && qt * 16 < T; qt += 4) {
     uint32_t obase = 0;   // opaque image bases: no hoisting of the unrolled body's LDS addresses
     asm volatile("" : "+v"(obase));
@@ -753,10 +842,12 @@ __global__ void __launch_bounds__(256) attn16_bwd_dq_k(const uint16_t* __restric
         for (int dt = 0; dt < 4; ++dt)
           dq[dt] = mfma(to_b16<H>(tr_frag(Kimg, 32 * c + 4 * g, 32 * c + 16 + 4 * g, dt * 16, lr)), bs, dq[dt]);
       }
-      if (qok) {
+      {
         const int64_t r = (row0 + q) * ld + h * DH;
+        float* pq = PT ? part_row(part, 0, nqh, b, qh, qt - qh * (FWD_QB / 16), nh, h) : nullptr;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) store_out(dqkv, dqkv16, r + dt * 16 + 4 * g, dq[dt], scale);
+        for (int dt = 0; dt < 4; ++dt)
+          store_out_part<PT>(dqkv, dqkv16, r + dt * 16 + 4 * g, dq[dt], scale, qok, pq, dt * 16 + 4 * g, lr);
       }
       continue;
     }
@@ -847,10 +938,12 @@ __global__ void __launch_bounds__(256) attn16_bwd_dq_k(const uint16_t* __restric
           dq[dt] = mfma(tr_frag(Kimg, 32 * c + 4 * g, 32 * c + 16 + 4 * g, dt * 16, lr), bs, dq[dt]);
       }
     }
-    if (qok) {
+    {
       const int64_t r = (row0 + q) * ld + h * DH;
+      float* pq = PT ? part_row(part, 0, nqh, b, qh, qt - qh * (FWD_QB / 16), nh, h) : nullptr;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store_out(dqkv, dqkv16, r + dt * 16 + 4 * g, dq[dt], dqs);
+      for (int dt = 0; dt < 4; ++dt)
+        store_out_part<PT>(dqkv, dqkv16, r + dt * 16 + 4 * g, dq[dt], dqs, qok, pq, dt * 16 + 4 * g, lr);
     }
   }
 }
@@ -898,6 +991,21 @@ int init_attrs_t() {
     rc |= set_lds(attn16_bwd_dq_k<0, H, TM, true>, fwd_lds<TM>());
     rc |= set_lds(attn16_bwd_dq_k<1, H, TM, true>, fwd_lds<TM>());
     rc |= set_lds(attn16_bwd_dq_k<2, H, TM, true>, fwd_lds<TM>());
+  }
+  // the bias-partial forms (PT)
+  rc |= set_lds(attn16_bwd_dkv_k<0, H, TM, true>, bwd_lds<TM>());
+  rc |= set_lds(attn16_bwd_dkv_k<1, H, TM, true>, bwd_lds<TM>());
+  rc |= set_lds(attn16_bwd_dkv2_k<0, H, TM, true>, bwd_lds<TM>());
+  rc |= set_lds(attn16_bwd_dkv2_k<1, H, TM, true>, bwd_lds<TM>());
+  rc |= set_lds(attn16_bwd_dq_k<0, H, TM, false, true>, fwd_lds<TM>());
+  rc |= set_lds(attn16_bwd_dq_k<1, H, TM, false, true>, fwd_lds<TM>());
+  if constexpr (TM == TMAX) {
+    rc |= set_lds(attn16_bwd_dkv_k<2, H, TM, true>, bwd_lds<TM>());
+    rc |= set_lds(attn16_bwd_dkv2_k<2, H, TM, true>, bwd_lds<TM>());
+    rc |= set_lds(attn16_bwd_dq_k<2, H, TM, false, true>, fwd_lds<TM>());
+    rc |= set_lds(attn16_bwd_dq_k<0, H, TM, true, true>, fwd_lds<TM>());
+    rc |= set_lds(attn16_bwd_dq_k<1, H, TM, true, true>, fwd_lds<TM>());
+    rc |= set_lds(attn16_bwd_dq_k<2, H, TM, true, true>, fwd_lds<TM>());
   }
   return rc;
 }
@@ -1019,8 +1127,10 @@ extern "C" int b2p_attn16_keep_masks(uint32_t* mask, const uint64_t* seeds, int6
 namespace {
 int attn16_bwd_launch(bool half, const void* qkv16, const void* dO16, const float* lse2, float* delta_ws, float* dqkv,
                       void* dqkv16, int64_t B, int64_t T, int64_t nh, int64_t dh, float scale, float drop_p,
-                      uint64_t drop_seed, const uint32_t* mask, b2p_stream_t stream) {
+                      uint64_t drop_seed, const uint32_t* mask, b2p_stream_t stream, float* part = nullptr) {
   B2P_CHECK_ARG(qkv16 && dO16 && lse2 && delta_ws && (dqkv || dqkv16), "attn16_bwd: NULL pointer");
+  B2P_CHECK_ARG(!part || FWD_QB == BWD_KB, "attn16_bwd: the bias partials need B2P_ATTN_QB = 128 (one row count for the three planes)");
+  B2P_CHECK_ARG(((uintptr_t)part & 15u) == 0, "attn16_bwd: bias_parts must be 16-byte aligned");
   B2P_CHECK_ARG(dh == DH && T <= 2 * TMAX && T > 0, "attn16_bwd: needs head size 64 and T <= 512");
   B2P_CHECK_ARG(!mask || T <= TMAX, "attn16_bwd: the stored keep mask covers T <= 256");
   if (B <= 0) return 0;
@@ -1031,40 +1141,45 @@ int attn16_bwd_launch(bool half, const void* qkv16, const void* dO16, const floa
   hipStream_t st = (hipStream_t)stream;
   const uint16_t *q = (const uint16_t*)qkv16, *d = (const uint16_t*)dO16;
   uint16_t* d16 = (uint16_t*)dqkv16;
-  auto run = [&](auto dm, auto hc) {
+  auto run = [&](auto dm, auto hc, auto ptc) {
     constexpr int DM = decltype(dm)::value;
     constexpr bool HH = decltype(hc)::value;
+    constexpr bool PT = decltype(ptc)::value;   // the forms that write the bias partials
     if (T <= TMAX) {
       if (T > TMAX - 16 && attn_t1())
-        hipLaunchKernelGGL((attn16_bwd_dq_k<DM, HH, TMAX, true>), grid_q, dim3(256), fwd_lds<TMAX>(), st, q, delta_ws,
-                           d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask);
+        hipLaunchKernelGGL((attn16_bwd_dq_k<DM, HH, TMAX, true, PT>), grid_q, dim3(256), fwd_lds<TMAX>(), st, q, delta_ws,
+                           d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask, part);
       else
-        hipLaunchKernelGGL((attn16_bwd_dq_k<DM, HH, TMAX>), grid_q, dim3(256), fwd_lds<TMAX>(), st, q, delta_ws, d,
-                           lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask);
+        hipLaunchKernelGGL((attn16_bwd_dq_k<DM, HH, TMAX, false, PT>), grid_q, dim3(256), fwd_lds<TMAX>(), st, q, delta_ws, d,
+                           lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask, part);
       if (attn_dkv2())
-        hipLaunchKernelGGL((attn16_bwd_dkv2_k<DM, HH, TMAX>), grid_k, dim3(256), bwd_lds<TMAX>(), st, q, delta_ws, d,
-                           lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask);
+        hipLaunchKernelGGL((attn16_bwd_dkv2_k<DM, HH, TMAX, PT>), grid_k, dim3(256), bwd_lds<TMAX>(), st, q, delta_ws, d,
+                           lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask, part);
       else
-        hipLaunchKernelGGL((attn16_bwd_dkv_k<DM, HH, TMAX>), grid_k, dim3(256), bwd_lds<TMAX>(), st, q, delta_ws, d,
-                           lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask);
+        hipLaunchKernelGGL((attn16_bwd_dkv_k<DM, HH, TMAX, PT>), grid_k, dim3(256), bwd_lds<TMAX>(), st, q, delta_ws, d,
+                           lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask, part);
     } else if constexpr (DM != 2) {
-      hipLaunchKernelGGL((attn16_bwd_dq_k<DM, HH, 2 * TMAX>), grid_q, dim3(256), fwd_lds<2 * TMAX>(), st, q, delta_ws,
-                         d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask);
+      hipLaunchKernelGGL((attn16_bwd_dq_k<DM, HH, 2 * TMAX, false, PT>), grid_q, dim3(256), fwd_lds<2 * TMAX>(), st, q, delta_ws,
+                         d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask, part);
       if (attn_dkv2())
-        hipLaunchKernelGGL((attn16_bwd_dkv2_k<DM, HH, 2 * TMAX>), grid_k, dim3(256), bwd_lds<2 * TMAX>(), st, q,
-                           delta_ws, d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask);
+        hipLaunchKernelGGL((attn16_bwd_dkv2_k<DM, HH, 2 * TMAX, PT>), grid_k, dim3(256), bwd_lds<2 * TMAX>(), st, q,
+                           delta_ws, d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask, part);
       else
-        hipLaunchKernelGGL((attn16_bwd_dkv_k<DM, HH, 2 * TMAX>), grid_k, dim3(256), bwd_lds<2 * TMAX>(), st, q,
-                           delta_ws, d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask);
+        hipLaunchKernelGGL((attn16_bwd_dkv_k<DM, HH, 2 * TMAX, PT>), grid_k, dim3(256), bwd_lds<2 * TMAX>(), st, q,
+                           delta_ws, d, lse2, dqkv, d16, (int)T, (int)nh, scale, dc, mask, part);
     }
   };
-  auto by_dm = [&](auto hc) {
-    if (drop_p > 0.f && mask) run(std::integral_constant<int, 2>(), hc);
-    else if (drop_p > 0.f) run(std::integral_constant<int, 1>(), hc);
-    else run(std::integral_constant<int, 0>(), hc);
+  auto by_dm = [&](auto hc, auto ptc) {
+    if (drop_p > 0.f && mask) run(std::integral_constant<int, 2>(), hc, ptc);
+    else if (drop_p > 0.f) run(std::integral_constant<int, 1>(), hc, ptc);
+    else run(std::integral_constant<int, 0>(), hc, ptc);
   };
-  if (half) by_dm(std::true_type());
-  else by_dm(std::false_type());
+  auto by_pt = [&](auto hc) {
+    if (part) by_dm(hc, std::true_type());
+    else by_dm(hc, std::false_type());
+  };
+  if (half) by_pt(std::true_type());
+  else by_pt(std::false_type());
   B2P_CHECK_LAUNCH();
   return 0;
 }
@@ -1087,4 +1202,18 @@ extern "C" int b2p_attn16_bwd_f16(const void* qkv16h, const void* dO16, const fl
                                   float drop_p, uint64_t drop_seed, const uint32_t* mask, b2p_stream_t stream) {
   return attn16_bwd_launch(true, qkv16h, dO16, lse2, delta_ws, dqkv, dqkv16, B, T, nh, dh, scale, drop_p, drop_seed,
                            mask, stream);
+}
+
+extern "C" int64_t b2p_attn16_bwd_bias_parts_rows(int64_t B, int64_t T, int64_t nh) {
+  (void)nh;   // one partial row per 16-row tile of a (batch, 128-row block): the heads share a row, 64 columns each
+  return B <= 0 || T <= 0 ? 0 : B * ((T + BWD_KB - 1) / BWD_KB) * PART_TILES;
+}
+
+extern "C" int b2p_attn16_bwd_parts(int qkv_fp16, const void* qkv16, const void* dO16, const float* lse2,
+                                    float* delta_ws, float* dqkv, void* dqkv16, float* bias_parts, int64_t B,
+                                    int64_t T, int64_t nh, int64_t dh, float scale, float drop_p, uint64_t drop_seed,
+                                    const uint32_t* mask, b2p_stream_t stream) {
+  B2P_CHECK_ARG(bias_parts, "attn16_bwd_parts: NULL bias_parts");
+  return attn16_bwd_launch(qkv_fp16 != 0, qkv16, dO16, lse2, delta_ws, dqkv, dqkv16, B, T, nh, dh, scale, drop_p,
+                           drop_seed, mask, stream, bias_parts);
 }

@@ -605,7 +605,8 @@ __global__ void __launch_bounds__(256) ln_rot16_k(const float* __restrict__ x, c
 constexpr int LN_BWD_ROWS = 16;   // rows per block (4 per wave): ~500 blocks at 8k rows
 // PF: prefetch the next row (the only form instantiated). MODE bits: 1 = dx_accum, 2 = dx_accum2, 4 = dxd
 // (compile-time, so a form holds registers only for the streams it reads: all three at once would not
-// fit two waves per SIMD)
+// fit two waves per SIMD). The dxd form with a NULL dxd pointer skips the fp32 store of the dropped dx
+// alone (a uniform branch: no stream, no register of its own), d16 and the dd partials stay
 constexpr int LNB_A1 = 1, LNB_A2 = 2, LNB_DXD = 4;
 template <bool PF, int MODE>
 __global__ void __launch_bounds__(256) ln_bwd_k(const float* __restrict__ dy, const float* __restrict__ x,
@@ -735,7 +736,8 @@ __global__ void __launch_bounds__(256) ln_bwd_k(const float* __restrict__ dy, co
           q.y = kk[1] ? o.y * dscale2 : 0.f;
           q.z = kk[2] ? o.z * dscale2 : 0.f;
           q.w = kk[3] ? o.w * dscale2 : 0.f;
-          reinterpret_cast<float4*>(dxd + row * cols)[c] = q;
+          // dxd NULL (uniform): the form without the fp32 image, for a caller that reads d16 and dd alone
+          if (dxd) reinterpret_cast<float4*>(dxd + row * cols)[c] = q;
           if (d16) reinterpret_cast<uint2*>(d16 + row * cols)[c] = b2p_pack_bf16x4(q);
           dd[i].x += q.x; dd[i].y += q.y; dd[i].z += q.z; dd[i].w += q.w;
         }
@@ -1305,13 +1307,28 @@ extern "C" int b2p_layernorm_bwd_gated(const float* dy, const float* x, const fl
                                        uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
                                        float* dbias_in, uint16_t* d16, const int32_t* dy_gate,
                                        const int32_t* acc2_gate, float* workspace, b2p_stream_t stream) {
+  return b2p_layernorm_bwd_flags(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, cols, dx_accum, dx_accum2, drop_p,
+                                 drop_seed, dx_dropped, in_drop_p, in_drop_seed, dbias_in, d16, dy_gate, acc2_gate,
+                                 0u, workspace, stream);
+}
+
+extern "C" int b2p_layernorm_bwd_flags(const float* dy, const float* x, const float* gamma, const float* mean,
+                                       const float* rstd, float* dx, float* dgamma, float* dbeta, int64_t rows,
+                                       int64_t cols, const float* dx_accum, const float* dx_accum2, float drop_p,
+                                       uint64_t drop_seed, float* dx_dropped, float in_drop_p, uint64_t in_drop_seed,
+                                       float* dbias_in, uint16_t* d16, const int32_t* dy_gate,
+                                       const int32_t* acc2_gate, uint32_t flags, float* workspace,
+                                       b2p_stream_t stream) {
+  B2P_CHECK_ARG((flags & ~(uint32_t)B2P_LNB_IN_DROP) == 0, "layernorm_bwd_flags: unknown flag");
+  // the dropout-input form is on with a dx_dropped destination (as ever) or under B2P_LNB_IN_DROP alone
+  const bool in_drop = dx_dropped || (flags & B2P_LNB_IN_DROP);
   B2P_CHECK_ARG(dy && x && gamma && mean && rstd && dx && workspace, "layernorm_bwd: NULL pointer");
   B2P_CHECK_ARG(cols % 4 == 0 && cols <= 64 * 4 * LN_MAXV, "layernorm_bwd: cols must be %%4 and <= 1024");
   B2P_CHECK_ARG(((uintptr_t)d16 & 7u) == 0, "layernorm_bwd: d16 must be 8-byte aligned");
   if (rows <= 0) return 0;
   const int nblk = (int)((rows + LN_BWD_ROWS - 1) / LN_BWD_ROWS);
   hipStream_t st = (hipStream_t)stream;
-  const int mode = (dx_accum ? LNB_A1 : 0) | (dx_accum2 ? LNB_A2 : 0) | (dx_dropped ? LNB_DXD : 0);
+  const int mode = (dx_accum ? LNB_A1 : 0) | (dx_accum2 ? LNB_A2 : 0) | (in_drop ? LNB_DXD : 0);
   hipLaunchKernelGGL(ln_bwd_kernel(mode), dim3(nblk), dim3(256), 0, st, dy, x, gamma, mean, rstd, dx, dx_accum, workspace,
                      rows, (int)cols, b2p_dropout_threshold(drop_p), drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f,
                      drop_seed, drop_p, dx_dropped, b2p_dropout_threshold(in_drop_p),
@@ -1320,9 +1337,9 @@ extern "C" int b2p_layernorm_bwd_gated(const float* dy, const float* x, const fl
   // partials [nblk][3][cols] -> dgamma | dbeta | dbias_in in one launch
   B2P_CHECK_ARG(((uintptr_t)dgamma & 15u) == 0 && ((uintptr_t)dbeta & 15u) == 0 && ((uintptr_t)dbias_in & 15u) == 0,
                 "layernorm_bwd: dgamma / dbeta / dbias_in must be 16-byte aligned");
-  if (dgamma || dbeta || (dx_dropped && dbias_in))   // else the caller sums the partials later
+  if (dgamma || dbeta || (in_drop && dbias_in))   // else the caller sums the partials later
     hipLaunchKernelGGL(ln_param_reduce_k, dim3((unsigned)((3 * cols + 127) / 128)), dim3(256), 0, st, workspace,
-                       nblk, (int)cols, dgamma, dbeta, dx_dropped ? dbias_in : nullptr);
+                       nblk, (int)cols, dgamma, dbeta, in_drop ? dbias_in : nullptr);
   B2P_CHECK_LAUNCH();
   return 0;
 }

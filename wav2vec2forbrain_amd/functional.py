@@ -1428,19 +1428,25 @@ def _ln_fwd16(x2d, g, b, eps, drop_p=0.0, seed=0, sel=None):
 
 
 def _ln_bwd16(dy, x, g, mean, rstd, need_params=True, dx_accum=None, drop_p=0.0, seed=0, in_drop_p=-1.0,
-              in_seed=0, dbias_in=None, dx_accum2=None, lazy=None, dy_gate=None, acc2_gate=None):
+              in_seed=0, dbias_in=None, dx_accum2=None, lazy=None, dy_gate=None, acc2_gate=None, want_dxd=True):
     """as _ln_bwd, plus d16 = bf16(dx_dropped if in_drop_p >= 0 else dx) (lazy: a sixth entry, the
     dropout-input bias gradient). LayerDrop's route folded in: a closed dy_gate stands for dy = 0, and
-    under acc2_gate dx_accum2 is added only when that gate is closed (b2p_layernorm_bwd_gated)."""
+    under acc2_gate dx_accum2 is added only when that gate is closed (b2p_layernorm_bwd_gated).
+    want_dxd=False: the dropout-input form without its fp32 image (b2p_layernorm_bwd_flags): the dxd slot
+    is None, every other result keeps its bits."""
     rows, cols = x.shape
     lz = _ln_lazy(lazy, need_params, dbias_in)
     dx = torch.empty_like(x)
     dg = torch.empty(cols, device=x.device) if need_params and not lz else None
     db = torch.empty(cols, device=x.device) if need_params and not lz else None
     ws = torch.empty(int(_lib.load().b2p_layernorm_bwd_workspace(rows, cols)), device=x.device)
-    dxd = torch.empty_like(x) if in_drop_p >= 0.0 else None
+    dxd = torch.empty_like(x) if in_drop_p >= 0.0 and want_dxd else None
     d16 = torch.empty(rows, cols, device=x.device, dtype=BF16)
-    if dy_gate is not None or acc2_gate is not None:
+    if in_drop_p >= 0.0 and not want_dxd:
+        _lib.call("b2p_layernorm_bwd_flags", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
+                  cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, None, float(in_drop_p), in_seed,
+                  None if lz else _p(dbias_in), _p(d16), _p(dy_gate), _p(acc2_gate), _lib.LNB_IN_DROP, _p(ws), _st())
+    elif dy_gate is not None or acc2_gate is not None:
         _lib.call("b2p_layernorm_bwd_gated", _p(dy), _p(x), _p(g), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), rows,
                   cols, _p(dx_accum), _p(dx_accum2), float(drop_p), seed, _p(dxd), float(max(in_drop_p, 0.0)),
                   in_seed, None if lz else _p(dbias_in), _p(d16), _p(dy_gate), _p(acc2_gate), _p(ws), _st())
@@ -2531,16 +2537,29 @@ def _attn16_fwd_f16(qkvh, B, T, nh, dh, p_attn, seed):
     return Oh, Ob, lse2, mask
 
 
-def _attn16_bwd(qkv16, dO16, lse2, B, T, nh, dh, p_attn, seed, want32=True, mask=None):
+_GRAD_IMG32 = [False]   # True (tests): the 16-bit layer backwards write the fp32 dxd / dqkv images they used to
+
+
+def _attn16_bwd(qkv16, dO16, lse2, B, T, nh, dh, p_attn, seed, want32=True, mask=None, bias_parts=False):
     """-> dqkv (B*T, 3D) f32 (or None) and its bf16 copy (mask: the forward's keep bits, or None to
-    re-hash). qkv16 fp16 (the _attn16_fwd_f16 forward) selects b2p_attn16_bwd_f16."""
+    re-hash). qkv16 fp16 (the _attn16_fwd_f16 forward) selects b2p_attn16_bwd_f16.
+    bias_parts: a third result, the Q / K / V bias gradients as three ColsumParts (the kernels' per-tile
+    column sums of the fp32 values, b2p_attn16_bwd_parts); with want32=False no fp32 image exists."""
     dev = qkv16.device
-    dqkv = torch.empty(B * T, 3 * nh * dh, device=dev) if want32 else None
-    d16 = torch.empty(B * T, 3 * nh * dh, device=dev, dtype=BF16)
+    D = nh * dh
+    dqkv = torch.empty(B * T, 3 * D, device=dev) if want32 else None
+    d16 = torch.empty(B * T, 3 * D, device=dev, dtype=BF16)
     delta = torch.empty(B, nh, T, device=dev)
+    mp = None if mask is None else mask.data_ptr()
+    if bias_parts:
+        P = int(_lib.load().b2p_attn16_bwd_bias_parts_rows(B, T, nh))
+        parts = torch.empty(3, P, D, device=dev)
+        _lib.call("b2p_attn16_bwd_parts", int(qkv16.dtype == torch.float16), _p(qkv16), _p(dO16), _p(lse2), _p(delta),
+                  _p(dqkv), _p(d16), _p(parts), B, T, nh, dh, float(dh ** -0.5), float(p_attn), seed, mp, _st())
+        return dqkv, d16, tuple(ColsumParts(parts[q]) for q in range(3))
     fn = "b2p_attn16_bwd_f16" if qkv16.dtype == torch.float16 else "b2p_attn16_bwd"
     _lib.call(fn, _p(qkv16), _p(dO16), _p(lse2), _p(delta), _p(dqkv), _p(d16), B, T, nh, dh,
-              float(dh ** -0.5), float(p_attn), seed, None if mask is None else mask.data_ptr(), _st())
+              float(dh ** -0.5), float(p_attn), seed, mp, _st())
     return dqkv, d16
 
 
@@ -2792,7 +2811,7 @@ class _EncoderLayer16(torch.autograd.Function):
         prm = ctx.prm
         dy2, dg2, dbe2, _dz2, dz2_16, db2 = _ln_bwd16(dout, y2, g2, m2, r2, True, in_drop_p=p_hid, in_seed=seeds[3],
                                                       dbias_in=db2, lazy=(prm[14], prm[15], prm[13] if ng[15] else None),
-                                                      dy_gate=ld_gate)
+                                                      dy_gate=ld_gate, want_dxd=_GRAD_IMG32[0])
         del _dz2
         dw2 = None
         if ng[14]:
@@ -2824,7 +2843,7 @@ class _EncoderLayer16(torch.autograd.Function):
         dy1, dg1, dbe1, _dz1, dz1_16, dbo = _ln_bwd16(dx1, y1, g1, m1, r1, True, in_drop_p=p_hid, in_seed=seeds[1],
                                                       dbias_in=dbo, dx_accum2=_skip_take(ctx.skip),
                                                       lazy=(prm[8], prm[9], prm[7] if ng[9] else None),
-                                                      acc2_gate=ld_gate)
+                                                      acc2_gate=ld_gate, want_dxd=_GRAD_IMG32[0])
         del _dz1
         dwo = None
         if ng[8]:
@@ -2833,10 +2852,18 @@ class _EncoderLayer16(torch.autograd.Function):
             else:
                 dwo = torch.empty_like(wo)
                 gemm(D, D, NT, op(dz1_16, 0, D, False), op(O16, 0, D, False), dwo, D)
+        # all three Q/K/V biases wanted (fused attention): their gradients come from the attention
+        # kernels' per-tile column sums and no fp32 dqkv image is written (only the bias sums read it)
+        bparts = None
+        b_parts = ctx.fused and not _GRAD_IMG32[0] and all(ctx.has_b[i] and ng[3 + 2 * i] for i in range(3))
         if ctx.fused:
             dO16 = torch.empty(NT, D, device=dev, dtype=BF16)
             gemm(NT, D, D, op(dz1_16, 0, D, True), op(wot16, 0, D, True), None, D, C16=dO16)
-            dqkv, dqkv16 = _attn16_bwd(qkv, dO16, P, B, T, nh, dh, p_attn, seeds[0], mask=Pd)
+            if b_parts:
+                dqkv, dqkv16, bparts = _attn16_bwd(qkv, dO16, P, B, T, nh, dh, p_attn, seeds[0], want32=False,
+                                                   mask=Pd, bias_parts=True)
+            else:
+                dqkv, dqkv16 = _attn16_bwd(qkv, dO16, P, B, T, nh, dh, p_attn, seeds[0], mask=Pd)
             del dO16
         else:
             dO = torch.empty(NT, D, device=dev)
@@ -2852,8 +2879,11 @@ class _EncoderLayer16(torch.autograd.Function):
             for i in range(3):
                 if ng[2 + 2 * i]:
                     grads_w[2 * i] = dwqkv[i * D:(i + 1) * D]
-        if all(ctx.has_b[i] and ng[3 + 2 * i] for i in range(3)) and _defer_bias_rows((prm[1], prm[3], prm[5]), dqkv, NT,
-                                                                                        3 * D):
+        if bparts is not None:   # frozen: finished in the side stream's batched accumulation; trained: _mat
+            for i in range(3):
+                grads_w[2 * i + 1] = bparts[i]
+        elif all(ctx.has_b[i] and ng[3 + 2 * i] for i in range(3)) and _defer_bias_rows((prm[1], prm[3], prm[5]), dqkv,
+                                                                                          NT, 3 * D):
             pass   # frozen Q/K/V biases: their column sums run on the side stream
         elif any(ctx.has_b[i] and ng[3 + 2 * i] for i in range(3)):
             dbqkv = torch.empty(3 * D, device=dev)
@@ -2872,6 +2902,8 @@ class _EncoderLayer16(torch.autograd.Function):
             if g is not None and k % 2 == 1 and _defer_ok(prm[k]):
                 _defer_acc(prm[k], g)
                 grads_w[k] = None
+            else:
+                grads_w[k] = _mat(g)
         for k, g in enumerate(rest):
             if g is not None and _defer_ok(prm[6 + k]):
                 _defer_acc(prm[6 + k], g)
@@ -3499,11 +3531,19 @@ class _ConformerAttnBlock(torch.autograd.Function):
         ng = ctx.needs_input_grad
         dz16, dbo = _drop_cast_colsum(dy, p_out, seeds[1], 1.0, ctx.has_b[3] and ng[10], lazy=True)
         dwo = _wgrad16(wo, ng[9], dz16, D, O if ctx.fused else cast16(O), D, NT)
+        need_b = [ctx.has_b[i] and ng[4 + 2 * i] for i in range(3)]
+        # all three biases wanted (fused attention): bias gradients from the attention kernels' per-tile
+        # column sums, no fp32 dqkv image (only the bias sums read it)
+        bparts = None
         if ctx.fused:
             # qkv / P / Pd / O hold qkv16, lse2, the dropout keep bits and O16 (forward)
             dO16 = torch.empty(NT, D, device=dev, dtype=BF16)
             gemm(NT, D, D, op(dz16, 0, D, True), op(weight16t(wo), 0, D, True), None, D, C16=dO16)
-            dqkv, dqkv16 = _attn16_bwd(qkv, dO16, P, B, T, nh, hd, p_attn, seeds[0], mask=Pd)
+            if all(need_b) and not _GRAD_IMG32[0]:
+                dqkv, dqkv16, bparts = _attn16_bwd(qkv, dO16, P, B, T, nh, hd, p_attn, seeds[0], want32=False,
+                                                   mask=Pd, bias_parts=True)
+            else:
+                dqkv, dqkv16 = _attn16_bwd(qkv, dO16, P, B, T, nh, hd, p_attn, seeds[0], mask=Pd)
             del dO16
         else:
             dO = torch.empty(NT, D, device=dev)
@@ -3521,15 +3561,17 @@ class _ConformerAttnBlock(torch.autograd.Function):
         else:
             hr16 = cast16(hr)
         grads = []
-        need_b = [ctx.has_b[i] and ng[4 + 2 * i] for i in range(3)]
         dbqkv = None
-        b_side = all(need_b) and _defer_bias_rows((ctx.prm[3], ctx.prm[5], ctx.prm[7]), dqkv, NT, 3 * D)
-        if all(need_b) and not b_side:   # the three bias gradients as one column reduction over dqkv
+        b_side = bparts is None and all(need_b) and _defer_bias_rows((ctx.prm[3], ctx.prm[5], ctx.prm[7]), dqkv, NT,
+                                                                     3 * D)
+        if bparts is None and all(need_b) and not b_side:   # one column reduction over dqkv for the three
             dbqkv = torch.empty(3 * D, device=dev)
             colsum(dqkv, NT, 3 * D, dbqkv)
         for i, (w, src16) in enumerate(((wq, hr16), (wk, hr16), (wv, h16))):
             gb = None
-            if b_side:
+            if bparts is not None:   # _defer_small: frozen -> the side stream's batched sum, trained -> _mat
+                gb = bparts[i]
+            elif b_side:
                 pass
             elif dbqkv is not None:
                 gb = dbqkv[i * D:(i + 1) * D]
