@@ -568,6 +568,42 @@ int b2p_attn16_bwd_parts(int qkv_fp16, const void* qkv16, const void* dO16, cons
                          int64_t dh, float scale, float drop_p, uint64_t drop_seed, const uint32_t* mask,
                          b2p_stream_t stream);
 
+/* ------------------------------------------------------------------ fused attention (exact fp32: the bf16x3 mode)
+ * The same operator on exact-fp32 MFMA (v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulate, bitwise an
+ * fmaf chain), csrc/attn32.hip: softmax(Q K^T * scale) -> dropout(p) -> @ V per (batch, head), no mask.
+ * Replaces eager_attention_forward behind HF Wav2Vec2Attention and the Conformer's rotary self-attention
+ * core (w2v_conformer_custom_feat_extractor.py:79-112) where the operands are fp32: the bf16x3 precision
+ * mode by default, the fp32 mode on request (functional.ATTN32_MODES). The unfused form runs 6 batched
+ * GEMMs and 2 softmax kernels per layer over (B, heads, T, T) fp32 tensors and saves two of them for the
+ * backward; these calls save lse2 alone.
+ * Head size 64 and 1 <= T <= 256 (b2p_attn32_supported): K and V of a head are 2 x 64 KB of LDS.
+ * qkv: f32 [B*T][3*nh*64] (q | k | v, head-major inside each), O: f32 [B*T][nh*64], lse2: f32 [B][nh][T]
+ * (row max + log2 of the row sum of the log2e-scaled scores, b2p_attn16_fwd's form; ln = lse2 * ln 2),
+ * dO: f32 [B*T][nh*64], dqkv: f32 [B*T][3*nh*64] = [dQ | dK | dV] laid out as qkv, delta_ws: 2*B*nh*T floats
+ * of workspace, two [B][nh][T] planes of row constants the dQ kernel forms from the values it recomputes
+ * and the dK/dV kernel reads: sum_key P_d dP_d, and 1 / (row sum of the probabilities recomputed from lse2).
+ * The second plane is why the backward matches the unfused path's precision: a row recomputed from one
+ * fp32 lse2 near 8 sums to 1 +- 6e-7, a row-coherent error ~6x the rounding noise of a stored P, which a
+ * full fine-tune's Adam trajectory follows; both kernels divide it out.
+ * qkv, O, dO and dqkv must be 16-byte aligned.
+ * Dropout keep mask = b2p_keep(seed', ((b*nh + h)*T + q)*TP + key, thr), TP = T rounded up to even
+ * (B*nh*T*TP < 2^32), thr = b2p_dropout_threshold(p), kept values scaled by 1/(1-p), seed' = the seed
+ * offset by the graph-replay step counter (b2p_set_seed_epoch): identical to b2p_softmax_fwd's, so the
+ * fused and unfused paths draw the same mask. The backward rehashes; no mask is stored.
+ * LayerDrop gate (b2p_set_gate, read on the device when the kernel runs): closed -> fwd writes O = 0 and
+ * lse2 = 0 and skips the work, bwd writes zeros over dqkv and delta_ws.
+ * fwd and the dQ kernel run one workgroup per (batch, head, 128 queries), the dK/dV kernel one per (batch,
+ * head, 128 keys). Rows >= T of the last block are neither computed into outputs nor stored; every element
+ * of O, lse2, delta_ws and dqkv is written exactly once per launch, without atomics, so runs repeat bit for
+ * bit. Stream-ordered, capturable, no allocation. NULL pointers, dh != 64, T outside [1, 256] and the
+ * 2^32 bound are rejected before any HIP call; B <= 0 returns 0. */
+int b2p_attn32_supported(int64_t T, int64_t dh);          /* 1: dh == 64 and 1 <= T <= 256 */
+int b2p_attn32_fwd(const float* qkv, float* O, float* lse2, int64_t B, int64_t T, int64_t nh, int64_t dh,
+                   float scale, float drop_p, uint64_t drop_seed, b2p_stream_t stream);
+int b2p_attn32_bwd(const float* qkv, const float* dO, const float* lse2, float* delta_ws, float* dqkv,
+                   int64_t B, int64_t T, int64_t nh, int64_t dh, float scale, float drop_p, uint64_t drop_seed,
+                   b2p_stream_t stream);
+
 /* ------------------------------------------------------------------ CTC
  * log_softmax + nn.CTCLoss(blank=0, reduction="mean", zero_infinity=True)
  * (src/model/w2v_custom_feat_extractor.py:59, 81-90). logits (B, T, C) batch-first; targets

@@ -1,7 +1,9 @@
 """Times the fused bf16 attention kernels at the bench shape (B=32, T=249, 12 heads x 64).
 usage: python tools/attn_bench.py [--parts] [B] [T] [nh]
 --parts: also the backward that leaves the Q/K/V bias gradients as per-tile partial sums and writes no fp32
-dqkv image (b2p_attn16_bwd_parts), beside the backward with the image plus the column sum that read it."""
+dqkv image (b2p_attn16_bwd_parts), beside the backward with the image plus the column sum that read it.
+usage: python tools/attn_bench.py --fp32
+the fp32 / bf16x3 modes' attention core: fused exact-fp32 kernels against the unfused GEMMs + softmax."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +24,39 @@ def timeit(f, n=10):
     return e0.elapsed_time(e1) / n * 1e3
 
 
+def fp32_ab():
+    """--fp32: the fp32 / bf16x3 modes' attention core, fused (csrc/attn32.hip) against unfused (6 batched GEMMs +
+    2 softmax kernels, functional.fused_attn32(False)), forward and backward, at the base and the Conformer-large
+    fine-tune shapes, in both modes; and the bytes each form keeps for the backward."""
+    dh = 64
+    Fn.ATTN32_MODES = (1, 3)   # the kernels against the fp32 mode's unfused form too (its default stays unfused)
+    for B, T, nh in ((32, 249, 12), (8, 249, 16)):
+        qkv = torch.randn(B * T, 3 * nh * dh, device="cuda") * 0.5
+        dO = torch.randn(B * T, nh * dh, device="cuda")
+        for mode in ("fp32", "bf16x3"):
+            for p in (0.0, 0.1):
+                res = {}
+                for fused in (True, False):
+                    with Fn.precision(mode), Fn.fused_attn32(fused):
+                        fwd = lambda: Fn._attn_core_fwd(qkv, B, T, nh, dh, p, 5)
+                        P, Pd, _ = fwd()
+                        assert (P.dim() == 3) == fused
+                        tf = timeit(fwd)
+                        tb = timeit(lambda: Fn._attn_core_bwd(qkv, P, Pd, dO, B, T, nh, dh, p, 5))
+                    kept = sum(t.numel() * t.element_size() for t in (P, Pd) if t is not None)
+                    res[fused] = (tf, tb, kept)
+                    del P, Pd
+                (ff, fb, fk), (uf, ub, uk) = res[True], res[False]
+                fl = 4.0 * B * nh * T * T * dh
+                print(f"attn32[{mode}] B={B} T={T} nh={nh} p={p}: fwd fused {ff:.1f} us ({fl / ff / 1e6:.0f} TFLOP/s) "
+                      f"unfused {uf:.1f} us; bwd fused {fb:.1f} us ({3.5 * fl / fb / 1e6:.0f} TFLOP/s) unfused {ub:.1f} us; "
+                      f"fwd+bwd {ff + fb:.1f} vs {uf + ub:.1f} us ({(uf + ub) / (ff + fb):.2f}x); kept for the backward "
+                      f"{fk / 1e6:.2f} MB vs {uk / 1e6:.2f} MB", flush=True)
+
+
+if "--fp32" in sys.argv:
+    fp32_ab()
+    sys.exit(0)
 PARTS = "--parts" in sys.argv
 argv = [a for a in sys.argv[1:] if a != "--parts"]
 B = int(argv[0]) if len(argv) > 0 else 32

@@ -2342,9 +2342,51 @@ def pos_conv_ln(e, wg, wv, cbias, ln_g, ln_b, groups, eps, drop_p, training):
 # attention core shared by the w2v and Conformer layers: softmax(Q K^T * scale) -> dropout -> @ V
 # qkv (B*T, 3D) laid out [b][t][q|k|v][h][dh]
 # =====================================================================================
+_FUSED_ATTN32 = [True]
+# The precision modes (GemmDesc.precision values) whose attention core takes the fused exact-fp32 kernels:
+# bf16x3, the Trainer's policy when the encoder itself is trained. The fp32 parity mode keeps the unfused
+# GEMMs + softmax bit for bit: its recorded full fine-tune trajectory (tests/test_configs34_gpu.py,
+# conformer_large_ft_bs8, gate 1e-4) sits at 5.4e-6 / 6.4e-5 (steps 2 / 3) unfused and moved to 3.6e-5 /
+# 2.0e-4 with the fused backward, although the fused step-1 gradients are the closer ones to the reference's
+# (median relative L2 over the parameters 9.8e-5 against 1.23e-4, equal sign-flip share 1.56 %): Adam's first
+# updates are ~lr * sign(g), so that gate follows which rounding a path has, not how much.
+# The kernels themselves serve either mode; tests and tools/attn_bench.py add 1 here to run them in fp32 mode.
+ATTN32_MODES = (3,)
+
+
+@contextlib.contextmanager
+def fused_attn32(on: bool = True):
+    """Whether the attention cores issued inside, in the modes of ATTN32_MODES (bf16x3), take the fused
+    exact-fp32 kernels (csrc/attn32.hip; the default) or the unfused batched GEMMs + softmax (tests and
+    tools/attn_bench.py run both forms in one process). The backward follows what its forward saved, not
+    this switch."""
+    old = _FUSED_ATTN32[0]
+    _FUSED_ATTN32[0] = bool(on)
+    try:
+        yield
+    finally:
+        _FUSED_ATTN32[0] = old
+
+
+def attn32_ok(T, dh) -> bool:
+    """The fused exact-fp32 attention kernels (csrc/attn32.hip, mirrors b2p_attn32_supported) cover head size 64 and
+    1 <= T' <= 256: K and V of one head as fp32 images are 2 x 64 KB of LDS."""
+    return dh == 64 and 1 <= T <= 256
+
+
 def _attn_core_fwd(qkv, B, T, nh, dh, p_attn, seed, want16=False):
+    """returns (P, Pd, O) of the unfused form, or (lse2, None, O) of the fused exact-fp32 form: taken in the
+    modes of ATTN32_MODES (bf16x3) for attn32_ok shapes under fused_attn32() when no 16-bit copy of O is wanted. The
+    fused kernels run every product on the exact fp32-operand MFMA and ignore the bf16x3 role forms
+    (x3_forms, B2P_X3_POLICY, DIAG_SWITCHES): they are at least as precise as any form the unfused GEMMs run
+    under. lse2 is (B, nh, T), where P would be 4-D: _attn_core_bwd tells the forms apart by that."""
     D = nh * dh
     dev = qkv.device
+    if _state.prec in ATTN32_MODES and not want16 and _FUSED_ATTN32[0] and attn32_ok(T, dh):
+        O = torch.empty(B * T, D, device=dev)
+        lse2 = torch.empty(B, nh, T, device=dev)
+        _lib.call("b2p_attn32_fwd", _p(qkv), _p(O), _p(lse2), B, T, nh, dh, dh ** -0.5, float(p_attn), seed, _st())
+        return lse2, None, O
     Tp = (T + 3) // 4 * 4
     S = torch.empty(B, nh, T, Tp, device=dev)
     gemm(T, T, dh, op(qkv, 0, 3 * D, True, bs1=T * 3 * D, bs2=dh), op(qkv, D, 3 * D, True, bs1=T * 3 * D, bs2=dh),
@@ -2363,9 +2405,18 @@ def _attn_core_fwd(qkv, B, T, nh, dh, p_attn, seed, want16=False):
 
 
 def _attn_core_bwd(qkv, P, Pd, dO, B, T, nh, dh, p_attn, seed, want16=False):
-    """returns dqkv (B*T, 3D) = [dQ | dK | dV] (and its bf16 copy when want16)"""
+    """returns dqkv (B*T, 3D) = [dQ | dK | dV] (and its bf16 copy when want16). A 3-D P is the fused
+    forward's lse2 (B, nh, T): the backward is then b2p_attn32_bwd whatever the mode is by now (_prec_follow
+    and the attribution switches may change it between forward and backward)."""
     D = nh * dh
     dev = qkv.device
+    if P.dim() == 3:
+        assert not want16, "the fused exact-fp32 attention keeps no 16-bit copies"
+        dqkv = torch.empty(B * T, 3 * D, device=dev)
+        delta = torch.empty(2, B, nh, T, device=dev)   # delta, 1 / row sum (b2p_hip.h)
+        _lib.call("b2p_attn32_bwd", _p(qkv), _p(dO), _p(P), _p(delta), _p(dqkv), B, T, nh, dh, dh ** -0.5,
+                  float(p_attn), seed, _st())
+        return dqkv
     Tp = P.shape[-1]
     Pd = P if Pd is None else Pd
     scale = dh ** -0.5
