@@ -497,6 +497,31 @@ int b2p_gru_mc_status(const void* workspace, int32_t* status, int32_t code, b2p_
  * next launch on, so the other members time out (-1: off) */
 int b2p_gru_mc_debug_withhold(int member);
 
+/* Persistent exact-fp32 recurrence (csrc/gru32.hip) for the fp32-operand precision modes (bf16x3, fp32):
+ * the same structure (one launch for the whole time loop, H/32 member workgroups per (direction, 16 batch
+ * rows) with their W_hh slice resident in registers, state exchanged every step as tagged granules
+ * through L2, bounded polling) on v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation, fp32 exchanged
+ * state ({32-bit tag, one fp32} per granule), the per-step kernels' gate functions; nothing is rounded to
+ * 16 bits. The backward exchanges partial dh sums (each member multiplies its own W_hh rows, transposed,
+ * by its own dgh; every member adds the partials of its units in member order). Deterministic.
+ * Same tensors and layouts as b2p_gru_fwd / b2p_gru_bwd, so either form's backward consumes either
+ * form's saved state; bhh, h0 and dh0 may be NULL. H = 256 or 512 (b2p_gru32_supported).
+ * workspace: b2p_gru32_workspace(B, H, ndir) bytes (0 for an unsupported H or ndir), 16-byte aligned,
+ * zeroed by the call itself before its launches; its first int is the timeout flag (b2p_gru_mc_status
+ * folds it into the persistent status word), the second counts the recurrences found on one XCD.
+ * A launch holds at most 128 workgroups (all must be resident); ndir * ceil(B/16) * (H/32) above that
+ * runs as successive launches over disjoint batch groups on the same stream. Stateless, stream-ordered,
+ * capturable. NULL pointers, an unsupported H, ndir outside {1, 2} and a misaligned workspace are rejected
+ * before any HIP call; B <= 0 or T <= 0 returns 0 without a launch. */
+int b2p_gru32_supported(int64_t H);
+int64_t b2p_gru32_workspace(int64_t B, int64_t H, int ndir);
+int b2p_gru_fwd32(const float* gi, const float* whh, const float* bhh, const float* h0, float* out,
+                  float* saved, void* workspace, int64_t B, int64_t T, int64_t H, int ndir,
+                  b2p_stream_t stream);
+int b2p_gru_bwd32(const float* dout, const float* whh, const float* out, const float* saved,
+                  const float* h0, float* dgi, float* dgh, float* dh0, void* workspace, int64_t B,
+                  int64_t T, int64_t H, int ndir, b2p_stream_t stream);
+
 /* ------------------------------------------------------------------ fused attention (bf16 mode)
  * softmax(Q K^T * scale) -> dropout(p) -> @ V per (batch, head), no mask (HF Wav2Vec2Attention,
  * TF w2v:438-463,529-545; the Conformer's rotary self-attention core, TF conf:458-470);

@@ -127,6 +127,10 @@ _SIGS = {
     "b2p_gru_bwd_mc": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p]),
     "b2p_gru_mc_status": (c_i32, [c_p, c_p, c_i32, c_p]),
     "b2p_gru_mc_debug_withhold": (c_i32, [c_i32]),
+    "b2p_gru32_supported": (c_i32, [c_i64]),
+    "b2p_gru32_workspace": (c_i64, [c_i64, c_i64, c_i32]),
+    "b2p_gru_fwd32": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p]),
+    "b2p_gru_bwd32": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p]),
     "b2p_gru_hprev": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p]),
     "b2p_attn16_fwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f32, c_f32, c_u64, c_p, c_p]),
     "b2p_attn16_fwd_f16": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f32, c_f32, c_u64, c_p, c_p]),

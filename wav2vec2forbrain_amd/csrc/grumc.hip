@@ -21,34 +21,16 @@
 // drop-in for b2p_gru_fwd / b2p_gru_bwd: gi, dgi, dgh [B][T][ndir*3H], out [B][T][ndir*H],
 // saved [B][T][ndir][4][H] = (r, z, n, W_hn h + b_hn), h0 / dh0 [ndir][B][H].
 #include "common.h"
+#include "gru_xch.h"   // granules, sweep, place, same_xcd, zero16_k: shared with csrc/gru32.hip
 #include "../../include/b2p_hip.h"
 
 namespace {
 constexpr int BG = 16;        // batch rows per recurrence (MFMA N)
 constexpr int UPM = 64;       // hidden units per member
-constexpr int NTH = 256;      // 4 waves x 16 units
-constexpr unsigned SPIN_MAX = 1u << 22;
-constexpr int IDS_PER_GROUP = 16;   // members' XCC ids (P <= 16)
+constexpr int NTH = XCH_NTH;  // 4 waves x 16 units
 constexpr int MAX_GROUPS = 32;      // (direction, 16-row batch group) recurrences per launch
 constexpr int64_t HDR_BYTES = 16 + (int64_t)MAX_GROUPS * IDS_PER_GROUP * 8;   // fail word + ids
 
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-
-// Granule stores: sc1 (write-through to memory: visible to any XCD) or, when every member of the
-// recurrence runs on this XCD (checked at launch, see same_xcd), a workgroup-scope store (sc0: the
-// line stays in the XCD's L2, where the other members' sc1 loads read it, ~2x closer than memory).
-__device__ __forceinline__ void store_granule(unsigned long long* p, unsigned long long x, bool local) {
-  if (local)
-    __hip_atomic_store((gu64*)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  else
-    __hip_atomic_store((gu64*)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void put_granule(unsigned long long* p, unsigned tag, unsigned v, bool local) {
-  store_granule(p, ((unsigned long long)tag << 32) | v, local);
-}
-__device__ __forceinline__ unsigned long long get_granule(const unsigned long long* p) {
-  return __hip_atomic_load((gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ unsigned pack2(float a, float b) {
   return (unsigned)b2p_bf16_bits(a) | ((unsigned)b2p_bf16_bits(b) << 16);
 }
@@ -64,91 +46,6 @@ __device__ __forceinline__ bf16x8 pack8_strided(const float* p, int64_t stride) 
 __device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 __device__ __forceinline__ float4 f4(const f32x4& a) { return make_float4(a[0], a[1], a[2], a[3]); }
-
-// Sweep N granules per lane (stride NTH, starting at this lane) until every tag == tag; the values
-// go to u32 LDS words at dst(q). On timeout the kernel records `fail` and stops waiting (the results
-// are then garbage, the launch still terminates); the caller folds `fail` into a persistent status
-// word right after the launch (b2p_gru_mc_status), which the host checks at its next sync and raises.
-template <int N, typename Tag, typename Dst>
-__device__ __forceinline__ void sweep(const unsigned long long* slot, Tag tag_ok, Dst dst, int* fail, bool& dead) {
-  static_assert(N <= 64, "one 64-bit pending mask per lane");
-  const int lane = threadIdx.x;
-  unsigned long long v[N];
-  unsigned long long miss = 0;   // granules of this lane not yet seen with this step's tag
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    v[k] = get_granule(slot + k * NTH + lane);
-    if (!tag_ok(v[k])) miss |= 1ull << k;
-  }
-  for (unsigned spins = 0; __any(miss != 0) && !dead; ++spins) {
-    if (spins > SPIN_MAX) {
-      dead = true;
-      if (lane == 0) __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }
-    __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      if (miss & (1ull << k)) {
-        v[k] = get_granule(slot + k * NTH + lane);
-        if (tag_ok(v[k])) miss &= ~(1ull << k);
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k) dst(k * NTH + lane, v[k]);
-}
-
-// recurrence (d, bg) and member of this block; false for blocks with no work
-__device__ __forceinline__ bool place(int P, int ngroups, int& d, int& bg, int& m, int nbg) {
-  int g;
-  if (ngroups <= 8) {   // members of a group on blocks with equal blockIdx % 8
-    g = blockIdx.x % 8;
-    m = blockIdx.x / 8;
-    if (g >= ngroups) return false;
-  } else {
-    g = blockIdx.x % ngroups;
-    m = blockIdx.x / ngroups;
-  }
-  d = g / nbg;
-  bg = g % nbg;
-  return m < P;
-}
-
-// Are all P members of this recurrence on one XCD? Each member publishes its XCC id once (sc1), every
-// member reads all of them; the answer is uniform across the group, so the group agrees on the store
-// flavour of every later granule. Placement is never assumed: any member elsewhere -> sc1 stores.
-__device__ __forceinline__ bool same_xcd(unsigned long long* ids, int P, int m, int* fail, bool& dead) {
-  __shared__ int all_same;
-  unsigned xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  xcc &= 0xFu;
-  if (threadIdx.x == 0) {
-    __hip_atomic_store((gu64*)(ids + m), (1ull << 32) | xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    all_same = 1;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {   // one wave polls the P ids
-    unsigned long long x = 0;
-    bool ok = threadIdx.x >= P;
-    for (unsigned spins = 0; !__all(ok); ++spins) {
-      if (spins > SPIN_MAX) {
-        dead = true;
-        if (threadIdx.x == 0) __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-      if (!ok) {
-        x = get_granule(ids + threadIdx.x);
-        ok = (unsigned)(x >> 32) == 1u;
-      }
-    }
-    if (threadIdx.x < P && (unsigned)x != xcc) all_same = 0;
-  }
-  __syncthreads();
-  const bool same = all_same != 0 && !dead;
-  if (same && m == 0 && threadIdx.x == 0) atomicAdd(fail + 1, 1);   // diagnostic: groups on one XCD
-  return same;
-}
 
 // ------------------------------------------------------------------------------------------ forward
 // exchange slots: [group][2][P * 512] granules (h_s of member m, batch b, unit pair p at
@@ -445,8 +342,6 @@ constexpr size_t fwd_lds() { return (size_t)2 * BG * (H / 2 + 4) * 4; }
 template <int H>
 constexpr size_t bwd_lds() { return (size_t)2 * BG * (3 * H + 8) * 2; }
 
-int grid_blocks(int P, int ngroups) { return ngroups <= 8 ? 8 * P : ngroups * P; }
-
 // test knob (b2p_gru_mc_debug_withhold): this member skips its granule stores, so the others time out
 int g_withhold = -1;
 
@@ -485,11 +380,6 @@ int launch_bwd(const float* dout, const float* whh, const float* out, const floa
 
 bool mc_supported(int64_t H) { return H == 256 || H == 384 || H == 512; }
 
-__global__ void zero16_k(uint4* __restrict__ p, int64_t n16) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = make_uint4(0u, 0u, 0u, 0u);
-}
-
 __global__ void mc_status_k(const int* __restrict__ fail, int32_t* status, int32_t code) {
   if (threadIdx.x == 0 && fail[0] != 0) atomicCAS(status, 0, code);
 }
@@ -521,13 +411,8 @@ extern "C" int64_t b2p_gru_mc_workspace(int64_t B, int64_t H, int ndir) {
 static int mc_prepare(void* ws, int64_t B, int64_t H, int ndir, hipStream_t st, unsigned long long** xch,
                       unsigned long long** ids, int** fail) {
   const int64_t bytes = b2p_gru_mc_workspace(B, H, ndir);
-  // every polled word (tags) and the fail flag are zeroed before every launch, by a kernel (a node of
-  // a captured graph, replayed first): granules of a previous launch never match this launch's tags.
-  // (A captured hipMemsetAsync node was observed leaving foreign bytes in the first 16 bytes of the
-  // block on replays after the first, ROCm 7.2.)
-  const int64_t n16 = bytes / 16;
-  const int64_t nb = (n16 + 255) / 256;
-  hipLaunchKernelGGL(zero16_k, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, st, (uint4*)ws, n16);
+  // every polled word (tags) and the fail flag are zeroed before every launch (gru_xch.h: zero16_k)
+  launch_zero16(ws, bytes, st);
   B2P_CHECK_LAUNCH();
   *fail = reinterpret_cast<int*>(ws);
   *ids = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16);

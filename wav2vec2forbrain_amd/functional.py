@@ -1542,10 +1542,34 @@ _GRUMC = [True]
 # diagnostic (tools/traj_err.py): None = the backward follows the forward's choice; True / False force
 # the multi-CU / per-step fp32 backward recurrence (same saved layout)
 _GRUMC_BWD = [None]
+# fp32-operand layers (not on the 16-bit path): the persistent exact-fp32 recurrences (csrc/gru32.hip)
+# instead of one launch per time step (csrc/gru.hip); False: the per-step kernels (A/B, tools/gru_bench.py)
+_GRU32 = [True]
+# precision modes (_state.prec) that take them: bf16x3. The fp32 parity mode keeps the per-step kernels
+# bit for bit: its recorded trajectories have a 1e-4 gate that another (equally accurate) summation
+# order can move past (the ATTN32_MODES decision); GRU32_MODES = (1, 3) is the request.
+GRU32_MODES = (3,)
+
+
+@contextlib.contextmanager
+def persistent_gru32(on: bool = True):
+    """Whether GRU layers issued inside, in the modes of GRU32_MODES (bf16x3) and off the 16-bit path,
+    take the persistent exact-fp32 recurrences (csrc/gru32.hip; the default) or the per-time-step kernels
+    (tests and A/B). A layer's backward follows its forward's choice (ctx.meta)."""
+    old = _GRU32[0]
+    _GRU32[0] = bool(on)
+    try:
+        yield
+    finally:
+        _GRU32[0] = old
 
 
 def _gru_mc_ws(B, H, ndir, dev):
     return torch.empty(int(_lib.load().b2p_gru_mc_workspace(B, H, ndir)), device=dev, dtype=torch.uint8)
+
+
+def _gru32_ws(B, H, ndir, dev):
+    return torch.empty(int(_lib.load().b2p_gru32_workspace(B, H, ndir)), device=dev, dtype=torch.uint8)
 
 
 # Multi-CU GRU timeouts (csrc/grumc.hip): a member that never publishes its state leaves the others
@@ -1573,7 +1597,7 @@ def _gru_mc_fold(ws, kind, whh0, H, dev):
 
 
 def _gru_status_error(code: int) -> RuntimeError:
-    kind = {1: "forward", 2: "backward"}.get(code // 65536, "?")
+    kind = {1: "forward", 2: "backward", 3: "exact-fp32 forward", 4: "exact-fp32 backward"}.get(code // 65536, "?")
     n, h = (code % 65536) // 16, {1: 256, 2: 384, 3: 512}.get(code % 16, "?")
     return RuntimeError(f"multi-CU GRU recurrence timed out ({kind} of GRU layer {n}, H={h}; recurrence id "
                         f"{code}): a member workgroup never published its state (not co-resident?), so the "
@@ -1648,6 +1672,9 @@ class _GRULayer(torch.autograd.Function):
         fast = bf16_mode() or (_state.prec == 3 and "grurec1" in (_state.x3forms or ()))
         use16 = fast and _GRU16[0] and bool(_lib.load().b2p_gru16_supported(H))
         usemc = fast and not use16 and _GRUMC[0] and bool(_lib.load().b2p_gru_mc_supported(H))
+        # fp32-operand layers: the persistent exact-fp32 recurrences (csrc/gru32.hip) in the GRU32_MODES
+        use32 = (not fast and _state.prec in GRU32_MODES and _GRU32[0]
+                 and bool(_lib.load().b2p_gru32_supported(H)))
         # the step's stacked recurrent weights / biases and the concatenated input-projection bias (with
         # b_hh's r/z parts folded in for gru16), assembled by ONE launch (b2p_gather_recs)
         whh_s = torch.empty(ndir, G3, H, device=dev)
@@ -1742,12 +1769,18 @@ class _GRULayer(torch.autograd.Function):
             _lib.call("b2p_gru_fwd_mc", _p(gi), _p(whh_s), _p(bhh_s), _p(h0), _p(out), _p(saved), _p(ws), B, T, H,
                       ndir, _st())
             _gru_mc_fold(ws, 1, whh[0], H, dev)
+        elif use32:
+            hL = None
+            ws = _gru32_ws(B, H, ndir, dev)
+            _lib.call("b2p_gru_fwd32", _p(gi), _p(whh_s), _p(bhh_s), _p(h0), _p(out), _p(saved), _p(ws), B, T, H,
+                      ndir, _st())
+            _gru_mc_fold(ws, 3, whh[0], H, dev)
         else:
             hL = None
             _lib.call("b2p_gru_fwd", _p(gi), _p(whh_s), _p(bhh_s), _p(h0), _p(out), _p(saved), B, T, H, ndir,
                       _st())
         ctx.save_for_backward(x, out, saved, whh_s, h0, wperm, hL, U16, *wih)
-        ctx.meta = (unf_meta, H, ndir, B, T, IN, bih[0] is not None, bhh[0] is not None, use16, usemc)
+        ctx.meta = (unf_meta, H, ndir, B, T, IN, bih[0] is not None, bhh[0] is not None, use16, usemc, use32)
         ctx.implicit = unf_meta is not None and implicit
         ctx.whh0 = whh[0]
         return out
@@ -1755,9 +1788,10 @@ class _GRULayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, out, saved, whh_s, h0, wperm, hL, U16, *wih = ctx.saved_tensors
-        unf_meta, H, ndir, B, T, IN, has_bih, has_bhh, use16, usemc = ctx.meta
+        unf_meta, H, ndir, B, T, IN, has_bih, has_bhh, use16, usemc, use32 = ctx.meta
         if not use16 and _GRUMC_BWD[0] is not None:
             usemc = _GRUMC_BWD[0] and bool(_lib.load().b2p_gru_mc_supported(H))
+            use32 = use32 and not usemc
         dev = out.device
         dout = dout.contiguous()
         G3 = 3 * H
@@ -1782,6 +1816,12 @@ class _GRULayer(torch.autograd.Function):
             _gru_bwd_launch(lambda: _lib.call("b2p_gru_bwd_mc", _p(dout), _p(whh_s), _p(out), _p(saved), _p(h0),
                                               _p(dgi), _p(dgh), _p(dh0), _p(ws), B, T, H, ndir, _st()))
             _gru_mc_fold(ws, 2, ctx.whh0, H, dev)
+        elif use32:
+            ws = _gru32_ws(B, H, ndir, dev)
+            # frozen-parameter gradient GEMMs beside the (H/32 per recurrence, at most 128)-CU recurrence
+            _gru_bwd_launch(lambda: _lib.call("b2p_gru_bwd32", _p(dout), _p(whh_s), _p(out), _p(saved), _p(h0),
+                                              _p(dgi), _p(dgh), _p(dh0), _p(ws), B, T, H, ndir, _st()))
+            _gru_mc_fold(ws, 4, ctx.whh0, H, dev)
         else:
             dhbuf = torch.empty(ndir, B, H, device=dev)
             _gru_bwd_launch(lambda: _lib.call("b2p_gru_bwd", _p(dout), _p(whh_s), _p(out), _p(saved), _p(h0), _p(dgi),
@@ -1886,7 +1926,9 @@ def gru_layer(x, H, ndir, weights, h0=None):
     x: (B,T,IN) tensor or Unfolded; weights: [w_ih, w_hh, b_ih, b_hh] per direction.
     In the bf16x3 mode with the 'gru1' form (the Trainer policy, X3_POLICY_FORMS) the layer runs as in the
     bf16 mode (persistent MFMA recurrences, fp16 forward operands) and its backward follows it
-    (_prec_follow: block 'gru'), instead of the fp32 operators' per-time-step recurrence kernels."""
+    (_prec_follow: block 'gru'), instead of the fp32 operators' recurrence kernels. Those are the persistent
+    exact-fp32 kernels (csrc/gru32.hip) in the modes of GRU32_MODES (bf16x3) for H = 256 / 512 under
+    persistent_gru32(), else one kernel per time step (csrc/gru.hip)."""
     with _fp32_if("gru"):
         ctxm = precision("bf16") if (_state.prec == 3 and "gru1" in (_state.x3forms or ())) else contextlib.nullcontext()
         with ctxm:
