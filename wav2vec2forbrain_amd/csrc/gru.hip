@@ -8,15 +8,13 @@
 // stages the 3*HU rows of W_hh and the BB rows of h_{t-1} in LDS and splits the K=H reduction
 // over its four waves; wave 0 then applies the gate nonlinearities (fp32 throughout).
 #include "common.h"
+#include "gru_dev.h"   // t_of
 #include "../../include/b2p_hip.h"
 
 namespace {
 constexpr int HU = 8;      // hidden units per block
 constexpr int BB = 8;      // batch rows per block
 constexpr int NTH = 256;   // 4 waves: K split in 4
-
-// time index of processing step s for direction d
-__device__ __forceinline__ int t_of(int s, int d, int T) { return d == 0 ? s : T - 1 - s; }
 
 // ------------------------------------------------------------------ forward step
 // gi [B][T][ndir*3H], whh [ndir][3H][H], bhh [ndir][3H], out [B][T][ndir*H],

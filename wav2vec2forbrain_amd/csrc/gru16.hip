@@ -22,17 +22,10 @@
 //   lane = (b % 16) + 16*((j % 16) / 4), i = j % 4, ub = j / 16, U = H/16, s = t (d=0) or T-1-t.
 // b2p_gru_lane_permute converts between the two layouts (bulk, HBM-bound).
 #include "common.h"
+#include "gru_dev.h"   // BG, sigm, tanh_fast, pack8_strided
 #include "../../include/b2p_hip.h"
 
 namespace {
-constexpr int BG = 16;   // batch rows per workgroup = MFMA N
-
-__device__ __forceinline__ bf16x8 pack8_strided(const float* p, int64_t stride) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)p[j * stride];
-  return r;
-}
 __device__ __forceinline__ void store_bf16x4(uint16_t* dst, float a, float b, float c, float d) {
   *reinterpret_cast<uint2*>(dst) = b2p_pack_bf16x4(make_float4(a, b, c, d));
 }
@@ -57,9 +50,6 @@ __device__ __forceinline__ void bst4(rsrc_t r, uint32_t off, float4 v) {
                                          0, 0);
 }
 
-// fast gate nonlinearities (v_exp_f32 + v_rcp_f32; ~1e-6 relative, well inside the bf16-mode budget)
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 // workgroup barrier for the LDS hand-off only: waits for this wave's LDS traffic (lgkmcnt) but not
 // for its outstanding global stores (__syncthreads would drain vmcnt every time step)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -451,36 +441,23 @@ __global__ void gru_lane_permute_k(const float* __restrict__ src, float* __restr
   }
 }
 
-template <int H>
-int launch_fwd(const float* giL, const float* whh, const float* bhh, const float* h0, float* hL, float* savL,
-               int64_t B, int64_t T, int ndir, hipStream_t st) {
+// one launch of `kernel` (its tensors in args, then the shape); the dynamic-LDS limit is raised once per kernel
+template <auto kernel, int H, size_t LDS, typename... A>
+int launch16(int64_t B, int64_t T, int ndir, hipStream_t st, A... args) {
   static bool attr = false;
-  const size_t shm = fwd_lds_bytes<H>();
   if (!attr) {
-    B2P_CHECK_HIP(hipFuncSetAttribute((const void*)gru16_fwd<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    B2P_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
     attr = true;
   }
   dim3 grid((unsigned)((B + BG - 1) / BG), (unsigned)ndir);
-  hipLaunchKernelGGL(gru16_fwd<H>, grid, dim3(H * 2), shm, st, giL, whh, bhh, h0, hL, savL, (int)B, (int)T, ndir);
+  hipLaunchKernelGGL(kernel, grid, dim3(H * 2), LDS, st, args..., (int)B, (int)T, ndir);
   B2P_CHECK_LAUNCH();
   return 0;
 }
-
-template <int H>
-int launch_bwd(const float* doL, const float* whh, const float* hL, const float* savL, const float* h0, float* dgL,
-               float* dh0, int64_t B, int64_t T, int ndir, hipStream_t st) {
-  static bool attr = false;
-  const size_t shm = bwd_lds_bytes<H>();
-  if (!attr) {
-    B2P_CHECK_HIP(hipFuncSetAttribute((const void*)gru16_bwd<H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    attr = true;
-  }
-  dim3 grid((unsigned)((B + BG - 1) / BG), (unsigned)ndir);
-  hipLaunchKernelGGL(gru16_bwd<H>, grid, dim3(H * 2), shm, st, doL, whh, hL, savL, h0, dgL, dh0, (int)B, (int)T,
-                     ndir);
-  B2P_CHECK_LAUNCH();
-  return 0;
-}
+template <int H, typename... A>
+int launch_fwd(A... a) { return launch16<gru16_fwd<H>, H, fwd_lds_bytes<H>()>(a...); }
+template <int H, typename... A>
+int launch_bwd(A... a) { return launch16<gru16_bwd<H>, H, bwd_lds_bytes<H>()>(a...); }
 static_assert(fwd_lds_bytes<256>() <= 160 * 1024, "fwd LDS");
 static_assert(bwd_lds_bytes<256>() <= 160 * 1024, "bwd LDS");
 
@@ -516,10 +493,10 @@ extern "C" int b2p_gru_fwd16(const float* giL, const float* whh, const float* bh
   B2P_CHECK_ARG(ln_bytes_ok(B, T, H, ndir, 4), "gru_fwd16: lane-native buffers exceed 2 GiB");
   if (B <= 0 || T <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (H == 32) return launch_fwd<32>(giL, whh, bhh, h0, hL, savL, B, T, ndir, st);
-  if (H == 64) return launch_fwd<64>(giL, whh, bhh, h0, hL, savL, B, T, ndir, st);
-  if (H == 128) return launch_fwd<128>(giL, whh, bhh, h0, hL, savL, B, T, ndir, st);
-  return launch_fwd<256>(giL, whh, bhh, h0, hL, savL, B, T, ndir, st);
+  if (H == 32) return launch_fwd<32>(B, T, ndir, st, giL, whh, bhh, h0, hL, savL);
+  if (H == 64) return launch_fwd<64>(B, T, ndir, st, giL, whh, bhh, h0, hL, savL);
+  if (H == 128) return launch_fwd<128>(B, T, ndir, st, giL, whh, bhh, h0, hL, savL);
+  return launch_fwd<256>(B, T, ndir, st, giL, whh, bhh, h0, hL, savL);
 }
 
 extern "C" int b2p_gru_bwd16(const float* doL, const float* whh, const float* hL, const float* savL, const float* h0,
@@ -530,8 +507,8 @@ extern "C" int b2p_gru_bwd16(const float* doL, const float* whh, const float* hL
   B2P_CHECK_ARG(ln_bytes_ok(B, T, H, ndir, 4), "gru_bwd16: lane-native buffers exceed 2 GiB");
   if (B <= 0 || T <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (H == 32) return launch_bwd<32>(doL, whh, hL, savL, h0, dgL, dh0, B, T, ndir, st);
-  if (H == 64) return launch_bwd<64>(doL, whh, hL, savL, h0, dgL, dh0, B, T, ndir, st);
-  if (H == 128) return launch_bwd<128>(doL, whh, hL, savL, h0, dgL, dh0, B, T, ndir, st);
-  return launch_bwd<256>(doL, whh, hL, savL, h0, dgL, dh0, B, T, ndir, st);
+  if (H == 32) return launch_bwd<32>(B, T, ndir, st, doL, whh, hL, savL, h0, dgL, dh0);
+  if (H == 64) return launch_bwd<64>(B, T, ndir, st, doL, whh, hL, savL, h0, dgL, dh0);
+  if (H == 128) return launch_bwd<128>(B, T, ndir, st, doL, whh, hL, savL, h0, dgL, dh0);
+  return launch_bwd<256>(B, T, ndir, st, doL, whh, hL, savL, h0, dgL, dh0);
 }

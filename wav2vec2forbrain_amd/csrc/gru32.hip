@@ -33,11 +33,11 @@
 // the backward keep the rest). ndir * ceil(B/16) * P above that runs as successive launches over
 // disjoint batch groups on the same stream, each on its own part of the workspace.
 #include "common.h"
+#include "gru_dev.h"   // BG, t_of
 #include "gru_xch.h"
 #include "../../include/b2p_hip.h"
 
 namespace {
-constexpr int BG = 16;             // batch rows per recurrence (MFMA N)
 constexpr int UPM = 32;            // hidden units per member
 constexpr int NTH = XCH_NTH;       // 4 waves
 constexpr int MGR = UPM * BG;      // granules one member publishes per step in the forward (512)
@@ -46,7 +46,6 @@ constexpr int LAUNCH_BUDGET = 128; // workgroups per launch
 __device__ __forceinline__ f32x4 mfma4(float a, float b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ int t_of(int s, int d, int T) { return d == 0 ? s : T - 1 - s; }
 
 // ------------------------------------------------------------------------------------------ forward
 // exchange slots: [group][2][P * 512] granules. h_s of member m, batch row b, unit u = 16ub + 4lq + i of m sits at
@@ -384,45 +383,34 @@ extern "C" int64_t b2p_gru32_workspace(int64_t B, int64_t H, int ndir) {
   return bwd_bytes(B < 0 ? 0 : B, H, ndir);   // sized for the backward (P times the forward's slots)
 }
 
+// The checks of both entry points, then the fail word, the ids and every polled slot (zero_bytes) zeroed before the
+// launches (a node of a captured graph) and the workspace carved. 0 go on, 1 / 2 error set, -1 nothing to do.
+static int prepare32(const char* who, bool pointers, void* ws, int64_t zero_bytes, int64_t B, int64_t T, int64_t H,
+                     int ndir, hipStream_t st, XchWs* w) {
+  if (int r = xch_check_args(who, pointers, supported32(H), H, "256 or 512", ndir, ws, B, T)) return r;
+  B2P_CHECK_ARG(B < (1ll << 24) && T < (1ll << 30), "%s: B or T out of range", who);
+  return xch_prepare(ws, hdr_bytes(B, ndir), zero_bytes, st, w);
+}
+
 extern "C" int b2p_gru_fwd32(const float* gi, const float* whh, const float* bhh, const float* h0, float* out,
                              float* saved, void* workspace, int64_t B, int64_t T, int64_t H, int ndir,
                              b2p_stream_t stream) {
-  B2P_CHECK_ARG(gi && whh && out && saved && workspace, "gru32 fwd: NULL pointer");
-  B2P_CHECK_ARG(supported32(H), "gru32 fwd: hidden size %lld unsupported (256 or 512)", (long long)H);
-  B2P_CHECK_ARG(ndir == 1 || ndir == 2, "gru32 fwd: ndir must be 1 or 2");
-  B2P_CHECK_ARG((((uintptr_t)workspace) & 15u) == 0, "gru32 fwd: workspace must be 16-byte aligned");
-  if (B <= 0 || T <= 0) return 0;
-  B2P_CHECK_ARG(B < (1ll << 24) && T < (1ll << 30), "gru32 fwd: B or T out of range");
   hipStream_t st = (hipStream_t)stream;
-  // fail word, ids and every polled slot zeroed before the launches (a node of a captured graph)
-  launch_zero16(workspace, fwd_bytes(B, H, ndir), st);
-  B2P_CHECK_LAUNCH();
-  int* fail = reinterpret_cast<int*>(workspace);
-  unsigned long long* ids = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + 16);
-  unsigned long long* xch = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + hdr_bytes(B, ndir));
-  if (H == 256)
-    return launch_chunks(gru32_fwd<256>, B, H, ndir, st, gi, whh, bhh, h0, out, saved, xch, ids, fail, (int)B, (int)T, ndir);
-  return launch_chunks(gru32_fwd<512>, B, H, ndir, st, gi, whh, bhh, h0, out, saved, xch, ids, fail, (int)B, (int)T, ndir);
+  XchWs w;
+  if (int r = prepare32("gru32 fwd", gi && whh && out && saved, workspace, fwd_bytes(B, H, ndir), B, T, H, ndir, st, &w))
+    return r < 0 ? 0 : r;
+  return launch_chunks(H == 256 ? gru32_fwd<256> : gru32_fwd<512>, B, H, ndir, st, gi, whh, bhh, h0, out, saved, w.xch,
+                       w.ids, w.fail, (int)B, (int)T, ndir);
 }
 
 extern "C" int b2p_gru_bwd32(const float* dout, const float* whh, const float* out, const float* saved,
                              const float* h0, float* dgi, float* dgh, float* dh0, void* workspace, int64_t B,
                              int64_t T, int64_t H, int ndir, b2p_stream_t stream) {
-  B2P_CHECK_ARG(dout && whh && out && saved && dgi && dgh && workspace, "gru32 bwd: NULL pointer");
-  B2P_CHECK_ARG(supported32(H), "gru32 bwd: hidden size %lld unsupported (256 or 512)", (long long)H);
-  B2P_CHECK_ARG(ndir == 1 || ndir == 2, "gru32 bwd: ndir must be 1 or 2");
-  B2P_CHECK_ARG((((uintptr_t)workspace) & 15u) == 0, "gru32 bwd: workspace must be 16-byte aligned");
-  if (B <= 0 || T <= 0) return 0;
-  B2P_CHECK_ARG(B < (1ll << 24) && T < (1ll << 30), "gru32 bwd: B or T out of range");
   hipStream_t st = (hipStream_t)stream;
-  launch_zero16(workspace, bwd_bytes(B, H, ndir), st);
-  B2P_CHECK_LAUNCH();
-  int* fail = reinterpret_cast<int*>(workspace);
-  unsigned long long* ids = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + 16);
-  unsigned long long* xch = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(workspace) + hdr_bytes(B, ndir));
-  if (H == 256)
-    return launch_chunks(gru32_bwd<256>, B, H, ndir, st, dout, whh, out, saved, h0, dgi, dgh, dh0, xch, ids, fail, (int)B,
-                         (int)T, ndir);
-  return launch_chunks(gru32_bwd<512>, B, H, ndir, st, dout, whh, out, saved, h0, dgi, dgh, dh0, xch, ids, fail, (int)B,
-                       (int)T, ndir);
+  XchWs w;
+  if (int r = prepare32("gru32 bwd", dout && whh && out && saved && dgi && dgh, workspace, bwd_bytes(B, H, ndir), B, T,
+                        H, ndir, st, &w))
+    return r < 0 ? 0 : r;
+  return launch_chunks(H == 256 ? gru32_bwd<256> : gru32_bwd<512>, B, H, ndir, st, dout, whh, out, saved, h0, dgi, dgh,
+                       dh0, w.xch, w.ids, w.fail, (int)B, (int)T, ndir);
 }

@@ -1,7 +1,8 @@
 // State exchange of the multi-CU persistent GRU recurrences (csrc/grumc.hip: 16-bit operands; csrc/gru32.hip:
 // exact fp32): tagged 8-byte granules written by one vector atomic store and polled with a bounded spin,
-// the placement of a recurrence's member workgroups, the one-XCD check that picks the store flavour, and
-// the kernel that zeroes a workspace before a launch. One copy of the bounded-spin path for both files.
+// the placement of a recurrence's member workgroups, the one-XCD check that picks the store flavour, the
+// kernel that zeroes a workspace before a launch, the workspace's carve-up and the entry points' shared
+// argument checks. One copy of the bounded-spin path for both files.
 #pragma once
 #include "common.h"
 
@@ -130,5 +131,28 @@ inline void launch_zero16(void* p, int64_t bytes, hipStream_t st) {
   const int64_t n16 = bytes / 16;
   const int64_t nb = (n16 + 255) / 256;
   hipLaunchKernelGGL(zero16_k, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, st, (uint4*)p, n16);
+}
+
+// workspace of one launch: [fail word block 16 B][ids: groups x IDS_PER_GROUP x 8 B][exchange slots]
+struct XchWs { int* fail; unsigned long long* ids; unsigned long long* xch; };
+// zeroes the first zero_bytes of ws on st and carves it (the slots start hdr_bytes in)
+inline int xch_prepare(void* ws, int64_t hdr_bytes, int64_t zero_bytes, hipStream_t st, XchWs* w) {
+  launch_zero16(ws, zero_bytes, st);
+  B2P_CHECK_LAUNCH();
+  char* p = reinterpret_cast<char*>(ws);
+  *w = {reinterpret_cast<int*>(p), reinterpret_cast<unsigned long long*>(p + 16),
+        reinterpret_cast<unsigned long long*>(p + hdr_bytes)};
+  return 0;
+}
+
+// Argument checks common to the four entry points (who: the name their error texts carry; sizes: the hidden
+// sizes they take). 0: go on, 1: error set, -1: nothing to do (empty batch or time).
+inline int xch_check_args(const char* who, bool pointers, bool h_ok, int64_t H, const char* sizes, int ndir,
+                          const void* ws, int64_t B, int64_t T) {
+  B2P_CHECK_ARG(pointers && ws, "%s: NULL pointer", who);
+  B2P_CHECK_ARG(h_ok, "%s: hidden size %lld unsupported (%s)", who, (long long)H, sizes);
+  B2P_CHECK_ARG(ndir == 1 || ndir == 2, "%s: ndir must be 1 or 2", who);
+  B2P_CHECK_ARG((((uintptr_t)ws) & 15u) == 0, "%s: workspace must be 16-byte aligned", who);
+  return B <= 0 || T <= 0 ? -1 : 0;
 }
 }  // namespace

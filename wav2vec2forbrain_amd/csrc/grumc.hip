@@ -21,11 +21,11 @@
 // drop-in for b2p_gru_fwd / b2p_gru_bwd: gi, dgi, dgh [B][T][ndir*3H], out [B][T][ndir*H],
 // saved [B][T][ndir][4][H] = (r, z, n, W_hn h + b_hn), h0 / dh0 [ndir][B][H].
 #include "common.h"
-#include "gru_xch.h"   // granules, sweep, place, same_xcd, zero16_k: shared with csrc/gru32.hip
+#include "gru_dev.h"   // BG, sigm, tanh_fast, pack8_strided
+#include "gru_xch.h"   // granules, sweep, place, same_xcd, workspace and argument checks: shared with csrc/gru32.hip
 #include "../../include/b2p_hip.h"
 
 namespace {
-constexpr int BG = 16;        // batch rows per recurrence (MFMA N)
 constexpr int UPM = 64;       // hidden units per member
 constexpr int NTH = XCH_NTH;  // 4 waves x 16 units
 constexpr int MAX_GROUPS = 32;      // (direction, 16-row batch group) recurrences per launch
@@ -37,14 +37,6 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {
 __device__ __forceinline__ unsigned pack2h(float a, float b) {
   return (unsigned)b2p_f16_bits(a) | ((unsigned)b2p_f16_bits(b) << 16);
 }
-__device__ __forceinline__ bf16x8 pack8_strided(const float* p, int64_t stride) {
-  bf16x8 r;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = (__bf16)p[j * stride];
-  return r;
-}
-__device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 __device__ __forceinline__ float4 f4(const f32x4& a) { return make_float4(a[0], a[1], a[2], a[3]); }
 
 // ------------------------------------------------------------------------------------------ forward
@@ -345,38 +337,24 @@ constexpr size_t bwd_lds() { return (size_t)2 * BG * (3 * H + 8) * 2; }
 // test knob (b2p_gru_mc_debug_withhold): this member skips its granule stores, so the others time out
 int g_withhold = -1;
 
-template <int H>
-int launch_fwd(const float* gi, const float* whh, const float* bhh, const float* h0, float* out, float* saved,
-               unsigned long long* xch, unsigned long long* ids, int* fail, int B, int T, int ndir, hipStream_t st) {
+// one launch of `kernel` (its tensors in args, then the carved workspace and the shape)
+template <auto kernel, int H, size_t LDS, typename... A>
+int launch_mc(const XchWs& w, int B, int T, int ndir, hipStream_t st, A... args) {
   static bool attr = false;
   if (!attr) {
-    B2P_CHECK_HIP(hipFuncSetAttribute((const void*)grumc_fwd<H>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)fwd_lds<H>()));
+    B2P_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
     attr = true;
   }
   const int nbg = (B + BG - 1) / BG;
-  hipLaunchKernelGGL(grumc_fwd<H>, dim3(grid_blocks(H / UPM, ndir * nbg)), dim3(NTH), fwd_lds<H>(), st, gi, whh, bhh,
-                     h0, out, saved, xch, ids, fail, B, T, ndir, nbg, g_withhold);
+  hipLaunchKernelGGL(kernel, dim3(grid_blocks(H / UPM, ndir * nbg)), dim3(NTH), LDS, st, args..., w.xch, w.ids, w.fail,
+                     B, T, ndir, nbg, g_withhold);
   B2P_CHECK_LAUNCH();
   return 0;
 }
-
-template <int H>
-int launch_bwd(const float* dout, const float* whh, const float* out, const float* saved, const float* h0, float* dgi,
-               float* dgh, float* dh0, unsigned long long* xch, unsigned long long* ids, int* fail, int B, int T,
-               int ndir, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    B2P_CHECK_HIP(hipFuncSetAttribute((const void*)grumc_bwd<H>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)bwd_lds<H>()));
-    attr = true;
-  }
-  const int nbg = (B + BG - 1) / BG;
-  hipLaunchKernelGGL(grumc_bwd<H>, dim3(grid_blocks(H / UPM, ndir * nbg)), dim3(NTH), bwd_lds<H>(), st, dout, whh,
-                     out, saved, h0, dgi, dgh, dh0, xch, ids, fail, B, T, ndir, nbg, g_withhold);
-  B2P_CHECK_LAUNCH();
-  return 0;
-}
+template <int H, typename... A>
+int launch_fwd(A... a) { return launch_mc<grumc_fwd<H>, H, fwd_lds<H>()>(a...); }
+template <int H, typename... A>
+int launch_bwd(A... a) { return launch_mc<grumc_bwd<H>, H, bwd_lds<H>()>(a...); }
 
 bool mc_supported(int64_t H) { return H == 256 || H == 384 || H == 512; }
 
@@ -408,58 +386,40 @@ extern "C" int64_t b2p_gru_mc_workspace(int64_t B, int64_t H, int ndir) {
   return HDR_BYTES + (int64_t)ndir * nbg * 2 * P * 1024 * 8;   // sized for the backward (2x the forward)
 }
 
-static int mc_prepare(void* ws, int64_t B, int64_t H, int ndir, hipStream_t st, unsigned long long** xch,
-                      unsigned long long** ids, int** fail) {
-  const int64_t bytes = b2p_gru_mc_workspace(B, H, ndir);
-  // every polled word (tags) and the fail flag are zeroed before every launch (gru_xch.h: zero16_k)
-  launch_zero16(ws, bytes, st);
-  B2P_CHECK_LAUNCH();
-  *fail = reinterpret_cast<int*>(ws);
-  *ids = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 16);
-  *xch = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + HDR_BYTES);
-  return 0;
+// The checks of both entry points (max_T: the backward granule carries a 16-bit step tag, dgh_granule, and tags
+// 1..T must stay distinct), then every polled word (tags) and the fail flag zeroed (the backward's size in both
+// passes) and the workspace carved. 0 go on, 1 / 2 error set, -1 nothing to do.
+static int mc_prepare(const char* who, bool pointers, void* ws, int64_t B, int64_t T, int64_t max_T, int64_t H,
+                      int ndir, hipStream_t st, XchWs* w) {
+  if (int r = xch_check_args(who, pointers, mc_supported(H), H, "256, 384 or 512", ndir, ws, B, T)) return r;
+  const int nbg = (int)((B + BG - 1) / BG);
+  B2P_CHECK_ARG(grid_blocks((int)(H / UPM), ndir * nbg) <= 256 && ndir * nbg <= MAX_GROUPS,
+                "%s: more recurrences than CUs", who);
+  B2P_CHECK_ARG(T <= max_T, "%s: T = %lld exceeds the 16-bit step tag", who, (long long)T);
+  return xch_prepare(ws, HDR_BYTES, b2p_gru_mc_workspace(B, H, ndir), st, w);
 }
 
 extern "C" int b2p_gru_fwd_mc(const float* gi, const float* whh, const float* bhh, const float* h0, float* out,
                               float* saved, void* workspace, int64_t B, int64_t T, int64_t H, int ndir,
                               b2p_stream_t stream) {
-  B2P_CHECK_ARG(gi && whh && out && saved && workspace, "gru_fwd_mc: NULL pointer");
-  B2P_CHECK_ARG(mc_supported(H), "gru_fwd_mc: hidden size %lld unsupported (256, 384 or 512)", (long long)H);
-  B2P_CHECK_ARG(ndir == 1 || ndir == 2, "gru_fwd_mc: ndir must be 1 or 2");
-  B2P_CHECK_ARG((((uintptr_t)workspace) & 15u) == 0, "gru_fwd_mc: workspace must be 16-byte aligned");
-  if (B <= 0 || T <= 0) return 0;
-  const int nbg = (int)((B + BG - 1) / BG);
-  B2P_CHECK_ARG(grid_blocks((int)(H / UPM), ndir * nbg) <= 256 && ndir * nbg <= MAX_GROUPS,
-                "gru_fwd_mc: more recurrences than CUs");
   hipStream_t st = (hipStream_t)stream;
-  unsigned long long *xch, *ids;
-  int* fail;
-  if (mc_prepare(workspace, B, H, ndir, st, &xch, &ids, &fail)) return 2;
-  if (H == 256) return launch_fwd<256>(gi, whh, bhh, h0, out, saved, xch, ids, fail, (int)B, (int)T, ndir, st);
-  if (H == 384) return launch_fwd<384>(gi, whh, bhh, h0, out, saved, xch, ids, fail, (int)B, (int)T, ndir, st);
-  return launch_fwd<512>(gi, whh, bhh, h0, out, saved, xch, ids, fail, (int)B, (int)T, ndir, st);
+  XchWs w;
+  if (int r = mc_prepare("gru_fwd_mc", gi && whh && out && saved, workspace, B, T, INT64_MAX, H, ndir, st, &w))
+    return r < 0 ? 0 : r;
+  if (H == 256) return launch_fwd<256>(w, (int)B, (int)T, ndir, st, gi, whh, bhh, h0, out, saved);
+  if (H == 384) return launch_fwd<384>(w, (int)B, (int)T, ndir, st, gi, whh, bhh, h0, out, saved);
+  return launch_fwd<512>(w, (int)B, (int)T, ndir, st, gi, whh, bhh, h0, out, saved);
 }
 
 extern "C" int b2p_gru_bwd_mc(const float* dout, const float* whh, const float* out, const float* saved,
                               const float* h0, float* dgi, float* dgh, float* dh0, void* workspace, int64_t B,
                               int64_t T, int64_t H, int ndir, b2p_stream_t stream) {
-  B2P_CHECK_ARG(dout && whh && out && saved && dgi && dgh && workspace, "gru_bwd_mc: NULL pointer");
-  B2P_CHECK_ARG(mc_supported(H), "gru_bwd_mc: hidden size %lld unsupported (256, 384 or 512)", (long long)H);
-  B2P_CHECK_ARG(ndir == 1 || ndir == 2, "gru_bwd_mc: ndir must be 1 or 2");
-  B2P_CHECK_ARG((((uintptr_t)workspace) & 15u) == 0, "gru_bwd_mc: workspace must be 16-byte aligned");
-  if (B <= 0 || T <= 0) return 0;
-  const int nbg = (int)((B + BG - 1) / BG);
-  B2P_CHECK_ARG(grid_blocks((int)(H / UPM), ndir * nbg) <= 256 && ndir * nbg <= MAX_GROUPS,
-                "gru_bwd_mc: more recurrences than CUs");
-  // the backward granule carries a 16-bit step tag (dgh_granule): tags 1..T must stay distinct
-  B2P_CHECK_ARG(T + 1 <= 0xFFFF, "gru_bwd_mc: T = %lld exceeds the 16-bit step tag", (long long)T);
   hipStream_t st = (hipStream_t)stream;
-  unsigned long long *xch, *ids;
-  int* fail;
-  if (mc_prepare(workspace, B, H, ndir, st, &xch, &ids, &fail)) return 2;
-  if (H == 256)
-    return launch_bwd<256>(dout, whh, out, saved, h0, dgi, dgh, dh0, xch, ids, fail, (int)B, (int)T, ndir, st);
-  if (H == 384)
-    return launch_bwd<384>(dout, whh, out, saved, h0, dgi, dgh, dh0, xch, ids, fail, (int)B, (int)T, ndir, st);
-  return launch_bwd<512>(dout, whh, out, saved, h0, dgi, dgh, dh0, xch, ids, fail, (int)B, (int)T, ndir, st);
+  XchWs w;
+  if (int r = mc_prepare("gru_bwd_mc", dout && whh && out && saved && dgi && dgh, workspace, B, T, 0xFFFE, H, ndir,
+                         st, &w))
+    return r < 0 ? 0 : r;
+  if (H == 256) return launch_bwd<256>(w, (int)B, (int)T, ndir, st, dout, whh, out, saved, h0, dgi, dgh, dh0);
+  if (H == 384) return launch_bwd<384>(w, (int)B, (int)T, ndir, st, dout, whh, out, saved, h0, dgi, dgh, dh0);
+  return launch_bwd<512>(w, (int)B, (int)T, ndir, st, dout, whh, out, saved, h0, dgi, dgh, dh0);
 }

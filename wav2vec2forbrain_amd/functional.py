@@ -15,6 +15,7 @@ Operators (reference call sites in each docstring):
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import functools
 import ctypes
@@ -1534,16 +1535,16 @@ class Unfolded:
         return win.permute(0, 1, 3, 2).reshape(B, self.T, C * self.kernel)
 
 
-# persistent MFMA recurrence in bf16 mode (False selects the per-step fp32 kernels, for A/B checks)
-_GRU16 = [True]
-# hidden sizes one CU cannot hold (Conformer H = 512): the multi-CU persistent kernels (csrc/grumc.hip)
-# in bf16 mode (False: per-step kernels, for A/B checks; tools/traj_err.py)
+# ---- recurrence back-ends: "gru16" one-CU persistent MFMA kernels on lane-native layouts (csrc/gru16.hip), and
+# with the standard layouts (_GRU_BACKENDS) "step" one fp32 launch per time step (csrc/gru.hip), "mc" multi-CU
+# persistent 16-bit (csrc/grumc.hip), "gru32" multi-CU persistent exact fp32 (csrc/gru32.hip). _gru_recurrence
+# alone chooses (table: DESIGN.md section 5); the switches are for A/B checks.
+# hidden sizes one CU cannot hold (Conformer H = 512) take "mc" in bf16 mode (False: "step"; tools/traj_err.py)
 _GRUMC = [True]
 # diagnostic (tools/traj_err.py): None = the backward follows the forward's choice; True / False force
 # the multi-CU / per-step fp32 backward recurrence (same saved layout)
 _GRUMC_BWD = [None]
-# fp32-operand layers (not on the 16-bit path): the persistent exact-fp32 recurrences (csrc/gru32.hip)
-# instead of one launch per time step (csrc/gru.hip); False: the per-step kernels (A/B, tools/gru_bench.py)
+# fp32-operand layers (not on the 16-bit path) take "gru32" (False: "step"; tools/gru_bench.py)
 _GRU32 = [True]
 # precision modes (_state.prec) that take them: bf16x3. The fp32 parity mode keeps the per-step kernels
 # bit for bit: its recorded trajectories have a 1e-4 gate that another (equally accurate) summation
@@ -1555,7 +1556,7 @@ GRU32_MODES = (3,)
 def persistent_gru32(on: bool = True):
     """Whether GRU layers issued inside, in the modes of GRU32_MODES (bf16x3) and off the 16-bit path,
     take the persistent exact-fp32 recurrences (csrc/gru32.hip; the default) or the per-time-step kernels
-    (tests and A/B). A layer's backward follows its forward's choice (ctx.meta)."""
+    (tests and A/B). A layer's backward follows its forward's choice (ctx.recurrence)."""
     old = _GRU32[0]
     _GRU32[0] = bool(on)
     try:
@@ -1564,12 +1565,43 @@ def persistent_gru32(on: bool = True):
         _GRU32[0] = old
 
 
-def _gru_mc_ws(B, H, ndir, dev):
-    return torch.empty(int(_lib.load().b2p_gru_mc_workspace(B, H, ndir)), device=dev, dtype=torch.uint8)
+def _gru_recurrence(H: int) -> str:
+    """The recurrence back-end a GRU layer of hidden size H issued now takes: "gru16", "mc", "gru32" or
+    "step". Reads the precision state, the switches above and the library's shape classes; no device."""
+    lib = _lib.load()
+    # the 16-bit path: bf16 mode, and the bf16x3 mode's 'grurec1' form (X3_POLICY_FORMS: fp16 / bf16 MFMA on
+    # W_hh h with the input-projection and weight-gradient GEMMs kept in the mode's split-bf16 form)
+    fast = bf16_mode() or (_state.prec == 3 and "grurec1" in (_state.x3forms or ()))
+    if fast and lib.b2p_gru16_supported(H):
+        return "gru16"
+    if fast and _GRUMC[0] and lib.b2p_gru_mc_supported(H):
+        return "mc"
+    if not fast and _state.prec in GRU32_MODES and _GRU32[0] and lib.b2p_gru32_supported(H):
+        return "gru32"
+    return "step"
 
 
-def _gru32_ws(B, H, ndir, dev):
-    return torch.empty(int(_lib.load().b2p_gru32_workspace(B, H, ndir)), device=dev, dtype=torch.uint8)
+def _gru_recurrence_bwd(fwd: str, H: int) -> str:
+    """The backward's back-end for a layer whose forward took `fwd`: the same, unless the _GRUMC_BWD
+    diagnostic re-routes a standard-layout layer (they share the saved layout)."""
+    if fwd == "gru16" or _GRUMC_BWD[0] is None:
+        return fwd
+    if _GRUMC_BWD[0] and _lib.load().b2p_gru_mc_supported(H):
+        return "mc"
+    return "gru32" if fwd == "gru32" else "step"
+
+
+# Standard-layout back-ends: fwd(gi, whh, bhh, h0, out, saved, [buffer,] B, T, H, ndir, stream) and bwd(dout, whh,
+# out, saved, h0, dgi, dgh, dh0, [buffer,] ...). buffer: the exchange workspace sized by `workspace` (both passes)
+# or, with `dhbuf`, the backward's (ndir, B, H) running dh. kinds: the (forward, backward) status kinds folded.
+_GRUBackend = collections.namedtuple("_GRUBackend", "fwd bwd workspace dhbuf kinds label")
+_GRU_BACKENDS = {
+    "step": _GRUBackend("b2p_gru_fwd", "b2p_gru_bwd", None, True, (None, None), ""),
+    "mc": _GRUBackend("b2p_gru_fwd_mc", "b2p_gru_bwd_mc", "b2p_gru_mc_workspace", False, (1, 2), ""),
+    "gru32": _GRUBackend("b2p_gru_fwd32", "b2p_gru_bwd32", "b2p_gru32_workspace", False, (3, 4), "exact-fp32 "),
+}
+# a layer's sizes (L, C, ktaps, stride: the Unfold's, else None)
+_GRUShape = collections.namedtuple("_GRUShape", "B T IN H G3 N3 ndir dev L C ktaps stride")
 
 
 # Multi-CU GRU timeouts (csrc/grumc.hip): a member that never publishes its state leaves the others
@@ -1580,24 +1612,19 @@ _GRU_STATUS: dict = {}      # device -> int32[1]
 _GRU_LAYERS: dict = {}      # id(W_hh of direction 0) -> layer number (order of first use)
 
 
-def _gru_status_word(dev):
+def _gru_mc_fold(ws, kind, whh0, H, dev):
     st = _GRU_STATUS.get(dev)
     if st is None:
         st = _GRU_STATUS[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
-    return st
-
-
-def _gru_mc_code(kind: int, whh0, H: int) -> int:
     n = _GRU_LAYERS.setdefault(id(whh0), len(_GRU_LAYERS))
-    return kind * 65536 + (n % 4096) * 16 + {256: 1, 384: 2, 512: 3}.get(H, 0)
-
-
-def _gru_mc_fold(ws, kind, whh0, H, dev):
-    _lib.call("b2p_gru_mc_status", _p(ws), _p(_gru_status_word(dev)), _gru_mc_code(kind, whh0, H), _st())
+    code = kind * 65536 + (n % 4096) * 16 + {256: 1, 384: 2, 512: 3}.get(H, 0)
+    _lib.call("b2p_gru_mc_status", _p(ws), _p(st), code, _st())
 
 
 def _gru_status_error(code: int) -> RuntimeError:
-    kind = {1: "forward", 2: "backward", 3: "exact-fp32 forward", 4: "exact-fp32 backward"}.get(code // 65536, "?")
+    kinds = {k: be.label + word for be in _GRU_BACKENDS.values()
+             for k, word in zip(be.kinds, ("forward", "backward")) if k}
+    kind = kinds.get(code // 65536, "?")
     n, h = (code % 65536) // 16, {1: 256, 2: 384, 3: 512}.get(code % 16, "?")
     return RuntimeError(f"multi-CU GRU recurrence timed out ({kind} of GRU layer {n}, H={h}; recurrence id "
                         f"{code}): a member workgroup never published its state (not co-resident?), so the "
@@ -1636,12 +1663,180 @@ def loss_item(loss: torch.Tensor) -> float:
     return v
 
 
-def _ln_floats(B, T, H, ndir, R):
-    return int(_lib.load().b2p_gru16_lane_floats(B, T, H, ndir, R))
+def _gru_bwd_launch(launch) -> None:
+    """Launch a GRU recurrence backward (launch() on the current stream) with the frozen weight
+    gradients flushed beside it (flush_wgrad): after the recurrence launch, ordered after the event
+    before it. Flushed before the launch, or with the recurrence on a stream of its own, the step times
+    measured equal (base 14.49 / 14.49 / 14.47 ms, Conformer 66.11 / - / 65.96 ms:
+    profiles/r05ak_gru_bwd_mode_ab.txt)."""
+    ev = torch.cuda.Event()
+    ev.record()
+    launch()
+    flush_wgrad(ev)
 
 
-def _stack2(a, b):
-    return a.unsqueeze(0) if b is None else torch.stack([a, b], 0)
+def _gru_launch(name, backward, tensors, s, whh0):
+    """One standard-layout recurrence launch through _GRU_BACKENDS[name] (the backward with the frozen
+    weight-gradient GEMMs beside it), its timeout flag folded into the status word. Returns the launch's
+    buffer, which the caller holds as long as the launch's other tensors."""
+    be = _GRU_BACKENDS[name]
+    buf = None
+    if be.workspace is not None:
+        buf = torch.empty(int(getattr(_lib.load(), be.workspace)(s.B, s.H, s.ndir)), device=s.dev, dtype=torch.uint8)
+    elif backward and be.dhbuf:
+        buf = torch.empty(s.ndir, s.B, s.H, device=s.dev)
+    args = [_p(t) for t in tensors] + ([] if buf is None else [_p(buf)]) + [s.B, s.T, s.H, s.ndir]
+    if backward:
+        _gru_bwd_launch(lambda: _lib.call(be.bwd, *args, _st()))
+    else:
+        _lib.call(be.fwd, *args, _st())
+    if be.kinds[backward] is not None:
+        _gru_mc_fold(buf, be.kinds[backward], whh0, s.H, s.dev)
+    return buf
+
+
+def _ln_floats(s, R):
+    return int(_lib.load().b2p_gru16_lane_floats(s.B, s.T, s.H, s.ndir, R))
+
+
+# ---- input projection gi = x W_ih^T + b_ih of both directions, in three forms. A form's forward fills gi and
+# returns the tensors its backward wants kept beside x and W_ih; its backward returns (dx, [dW_ih per
+# direction]), None where not needed.
+class _DenseProj:
+    """x is (B, T, IN)."""
+
+    @staticmethod
+    def forward(x, wih, bias_cat, gi, s, need_dx):
+        _chk(x, "gru.x")
+        B, T, IN, G3, N3 = s.B, s.T, s.IN, s.G3, s.N3
+        if bf16_mode() and IN % 8 == 0:
+            # both directions' projections as ONE GEMM over the stacked 16-bit W_ih (fp16 under forward_f16)
+            half = _state.fwd16
+            w16 = torch.empty(N3, IN, device=s.dev, dtype=torch.float16 if half else BF16)
+            for d in range(s.ndir):
+                _lib.call("b2p_cast16_2d", _p(wih[d]), G3, IN, IN, _p(w16, d * G3 * IN), IN, int(half), _st())
+            x16 = torch.empty(B * T, IN, device=s.dev, dtype=w16.dtype)
+            _lib.call("b2p_cast16_2d", _p(x), B * T, IN, IN, _p(x16), IN, int(half), _st())
+            gemm(B * T, N3, IN, op(x16, 0, IN, True), op(w16, 0, IN, True), gi, N3, bias=bias_cat)
+        else:
+            for d in range(s.ndir):
+                gemm(B * T, G3, IN, op(x, 0, IN, True), op(wih[d], 0, IN, True), gi, N3, c_off=d * G3,
+                     bias=None if bias_cat is None else _view_off(bias_cat, d * G3))
+        return ()
+
+    @staticmethod
+    def backward(dgi, x, wih, kept, s, need_dx, need_dw):
+        B, T, IN, G3, N3 = s.B, s.T, s.IN, s.G3, s.N3
+        dx, dws = None, [None] * s.ndir
+        for d in range(s.ndir):
+            if need_dw[d]:
+                dws[d] = torch.empty(G3, IN, device=s.dev)
+                gemm(G3, IN, B * T, op(dgi, d * G3, N3, False), op(x, 0, IN, False), dws[d], IN)
+        if need_dx:
+            dx = torch.empty(B, T, IN, device=s.dev)
+            for d in range(s.ndir):
+                gemm(B * T, IN, G3, op(dgi, d * G3, N3, True), op(wih[d], 0, IN, False), dx, IN, beta=float(d > 0))
+        return dx, dws
+
+
+def _unfold_dw(dwp, s):
+    """Per-direction dW_ih (feature index c*k + tap) from the stacked tap-major weight gradient."""
+    dws = [torch.empty(s.G3, s.IN, device=s.dev) for _ in range(s.ndir)]
+    for d, dw in enumerate(dws):
+        _lib.call("b2p_conv_weight_permute", _p(dwp, d * s.G3 * s.IN), _p(dw), s.G3, s.C, s.ktaps, 1, _st())
+    return dws
+
+
+class _UnfoldProj:
+    """x is the (B, L, C) source of an Unfold(k, stride), materialised tap-major: as bf16 rows (U16, also the
+    weight-gradient operand) in bf16 mode; by the fp32-operand kernel's staging (conv_op), which rounds there,
+    in fp32 mode and under forward_f16."""
+
+    @staticmethod
+    def forward(x, wih, bias_cat, gi, s, need_dx):
+        B, T, IN, G3, N3, L, C = s.B, s.T, s.IN, s.G3, s.N3, s.L, s.C
+        # tap-major weight copy: W'[n][tap*C + c] = W[n][c*k + tap] for both directions
+        wperm = torch.empty(N3, IN, device=s.dev)
+        for d in range(s.ndir):
+            _lib.call("b2p_conv_weight_permute", _p(wih[d]), _p(wperm, d * G3 * IN), G3, C, s.ktaps, 0, _st())
+        U16 = None
+        if bf16_mode() and not _state.fwd16:
+            U16 = torch.empty(B * T, IN, device=s.dev, dtype=BF16)
+            _lib.call("b2p_unfold16", _p(x), _p(U16), B, L, C, s.ktaps, s.stride, _st())
+            wperm = cast16(wperm)
+            A = op(U16, 0, IN, True)
+        else:
+            A = conv_op(x, 0, C, T, L, s.stride, 0, IN, L * C, True)
+            A.conv_Cg = C  # inner j = tap*C + c
+        gemm(B * T, N3, IN, A, op(wperm, 0, IN, True), gi, N3, bias=bias_cat)
+        return wperm, U16
+
+    @staticmethod
+    def backward(dgi, x, wih, kept, s, need_dx, need_dw):
+        B, T, IN, N3, L, C = s.B, s.T, s.IN, s.N3, s.L, s.C
+        wperm, U16 = kept
+        dg = cast16(dgi) if U16 is not None else dgi   # the dgi operand, in the Unfold operand's format
+        dx, dws = None, [None] * s.ndir
+        if any(need_dw):
+            dwp = torch.empty(N3, IN, device=s.dev)
+            U = op(U16, 0, IN, False) if U16 is not None else conv_op(x, 0, C, T, L, s.stride, 0, C, L * C, False)
+            gemm(N3, IN, B * T, op(dg, 0, N3, False), U, dwp, IN)
+            dws = _unfold_dw(dwp, s)
+        if need_dx:
+            dA = torch.empty(B * T, IN, device=s.dev)
+            gemm(B * T, IN, N3, op(dg, 0, N3, True), op(wperm, 0, IN, False), dA, IN)
+            dx = torch.empty(B, L, C, device=s.dev)
+            _lib.call("b2p_unfold_col2im", _p(dA), None, _p(dx), B, L, C, T, s.ktaps, s.stride, _st())
+        return dx, dws
+
+
+class _ImplicitUnfoldProj:
+    """bf16 mode's layer 0 (csrc/elementwise.hip "implicit Unfold operands"): the GEMM reads a 16-bit copy of the
+    (B, L, C) source through an overlapping-row view (row stride stride*C); fp16 operands under forward_f16."""
+
+    @staticmethod
+    def forward(x, wih, bias_cat, gi, s, need_dx):
+        B, T, IN, N3, L, C, ktaps, stride = s.B, s.T, s.IN, s.N3, s.L, s.C, s.ktaps, s.stride
+        half = _state.fwd16
+        wf = torch.empty(N3, IN, device=s.dev, dtype=torch.float16 if half else BF16)
+        # the backward-data operand of the same weights, written in the same pass when needed
+        wperm = torch.empty((ktaps // stride) * N3, stride * C, device=s.dev, dtype=BF16) if need_dx else None
+        _lib.call("b2p_unfold_weight16", _p(wih[0]), _p(wih[1]) if s.ndir == 2 else None, s.G3, C, ktaps, stride,
+                  _p(wf), int(half), _p(wperm), _st())
+        s16 = _ImplicitUnfoldProj.source16(x, s, half)
+        gemm(T, N3, IN, op(s16, 0, stride * C, True, bs1=L * C), op(wf, 0, IN, True), gi, N3, cbs1=T * N3, nz1=B,
+             bias=bias_cat)
+        return wperm, (None if half else s16)    # the bf16 copy doubles as the weight-gradient operand
+
+    @staticmethod
+    def source16(x, s, half):
+        n_s, tail = s.B * s.L * s.C, (s.ktaps - s.stride) * s.C
+        s16 = torch.empty(n_s + tail, device=s.dev, dtype=torch.float16 if half else BF16)
+        _lib.call("b2p_cast16_tail", _p(x), _p(s16), n_s, n_s + tail, int(half), _st())
+        return s16
+
+    @staticmethod
+    def backward(dgi, x, wih, kept, s, need_dx, need_dw):
+        # dgi in the padded row layout (k/s - 1 zero rows in front, L/s rows per sample, rows t >= T
+        # zero): the weight gradient reads it as the k-major A operand, the input gradient as the
+        # overlapping-row view (one GEMM straight into dx, no col2im)
+        B, IN, N3, L, C, ktaps, stride = s.B, s.IN, s.N3, s.L, s.C, s.ktaps, s.stride
+        wperm, s16 = kept
+        R, lead = L // stride, ktaps // stride - 1
+        dgp = torch.empty((lead + B * R) * N3, device=s.dev, dtype=BF16)
+        _lib.call("b2p_pad_rows16", _p(dgi), _p(dgp), B, s.T, N3, R, lead, _st())
+        dx, dws = None, [None] * s.ndir
+        if any(need_dw):
+            s16 = s16 if s16 is not None else _ImplicitUnfoldProj.source16(x, s, False)
+            dwp = torch.empty(N3, IN, device=s.dev)
+            gemm(N3, IN, B * R, op(dgp, lead * N3, N3, False), op(s16, 0, stride * C, False), dwp, IN)
+            del s16
+            dws = _unfold_dw(dwp, s)
+        if need_dx:
+            dx = torch.empty(B, L, C, device=s.dev)
+            gemm(B * R, stride * C, (ktaps // stride) * N3, op(dgp, 0, N3, True), op(wperm, 0, stride * C, False),
+                 dx, stride * C)
+        return dx, dws
 
 
 @_prec_follow
@@ -1649,185 +1844,94 @@ class _GRULayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, unf_meta, H, ndir, h0, *weights):
         # weights: per direction (w_ih, w_hh, b_ih, b_hh)  (b_* may be None)
-        dev = x.device
+        dev, G3 = x.device, 3 * H
         if unf_meta is not None:
             ktaps, stride = unf_meta
             B, L, C = x.shape
-            T = (L - ktaps) // stride + 1
-            IN = C * ktaps
+            s = _GRUShape(B, (L - ktaps) // stride + 1, C * ktaps, H, G3, ndir * G3, ndir, dev, L, C, ktaps, stride)
         else:
-            B, T, IN = x.shape
-        G3 = 3 * H
-        wih = [weights[4 * d + 0] for d in range(ndir)]
-        whh = [weights[4 * d + 1] for d in range(ndir)]
-        bih = [weights[4 * d + 2] for d in range(ndir)]
-        bhh = [weights[4 * d + 3] for d in range(ndir)]
+            s = _GRUShape(*x.shape, H, G3, ndir * G3, ndir, dev, None, None, None, None)
+        B, T = s.B, s.T
+        wih, whh, bih, bhh = ([weights[4 * d + i] for d in range(ndir)] for i in range(4))
         for w in wih + whh:
             _chk(w, "gru.weight")
         gi = torch.empty(B, T, ndir * G3, device=dev)
-        # bf16 mode: persistent MFMA recurrence (csrc/gru16.hip), which wants b_hh's r/z parts folded
-        # into the input projection bias
-        # the bf16x3 mode's 'grurec1' form (X3_POLICY_FORMS): the persistent recurrences (fp16 / bf16 MFMA on
-        # W_hh h) with the input-projection and weight-gradient GEMMs kept in the mode's split-bf16 form
-        fast = bf16_mode() or (_state.prec == 3 and "grurec1" in (_state.x3forms or ()))
-        use16 = fast and _GRU16[0] and bool(_lib.load().b2p_gru16_supported(H))
-        usemc = fast and not use16 and _GRUMC[0] and bool(_lib.load().b2p_gru_mc_supported(H))
-        # fp32-operand layers: the persistent exact-fp32 recurrences (csrc/gru32.hip) in the GRU32_MODES
-        use32 = (not fast and _state.prec in GRU32_MODES and _GRU32[0]
-                 and bool(_lib.load().b2p_gru32_supported(H)))
-        # the step's stacked recurrent weights / biases and the concatenated input-projection bias (with
-        # b_hh's r/z parts folded in for gru16), assembled by ONE launch (b2p_gather_recs)
+        rec = _gru_recurrence(H)
+        # 1. the step's stacked recurrent weights / biases and the concatenated input-projection bias (with
+        # b_hh's r/z parts folded in for gru16, which wants them there), assembled by ONE launch
+        fold = rec == "gru16" and bhh[0] is not None
         whh_s = torch.empty(ndir, G3, H, device=dev)
         bhh_s = torch.empty(ndir, G3, device=dev) if bhh[0] is not None else None
-        has_bias = any(b is not None for b in bih) or (use16 and bhh[0] is not None)
-        bias_cat = torch.empty(ndir * G3, device=dev) if has_bias else None
+        bias_cat = torch.empty(ndir * G3, device=dev) if (any(b is not None for b in bih) or fold) else None
         recs = []
         for d in range(ndir):
             recs += [_p(whh_s, d * G3 * H), _p(whh[d]), 0, G3 * H]
             if bhh_s is not None:
                 recs += [_p(bhh_s, d * G3), _p(bhh[d]), 0, G3]
             if bias_cat is not None:
-                fold = use16 and bhh[0] is not None
                 recs += [_p(bias_cat, d * G3), _p(bih[d]) or 0, _p(bhh[d]) if fold else 0, 2 * H,
                          _p(bias_cat, d * G3 + 2 * H), _p(bih[d], 2 * H) or 0, 0, H]
         arr = (ctypes.c_int64 * len(recs))(*recs)
         _lib.call("b2p_gather_recs", arr, len(recs) // 4, _st())
-        # bf16 mode's layer 0 reads the Unfold through an implicit overlapping-row view
+        # 2. input projection; bf16 mode's layer 0 reads the Unfold through an implicit overlapping-row view
         implicit = unf_meta is not None and bf16_mode() and L % stride == 0 and ktaps % stride == 0 and C % 4 == 0
-        if implicit:
-            # implicit Unfold (csrc/elementwise.hip "implicit Unfold operands"): the GEMM reads a 16-bit copy
-            # of x through an overlapping-row view (row stride stride*C); fp16 operands under forward_f16
-            half = _state.fwd16
-            N3 = ndir * G3
-            wf = torch.empty(N3, IN, device=dev, dtype=torch.float16 if half else BF16)
-            # the backward-data operand of the same weights, written in the same pass when needed
-            wperm = (torch.empty((ktaps // stride) * N3, stride * C, device=dev, dtype=BF16)
-                     if ctx.needs_input_grad[0] else None)
-            _lib.call("b2p_unfold_weight16", _p(wih[0]), _p(wih[1]) if ndir == 2 else None, G3, C, ktaps, stride,
-                      _p(wf), int(half), _p(wperm), _st())
-            n_s, tail = B * L * C, (ktaps - stride) * C
-            s16 = torch.empty(n_s + tail, device=dev, dtype=torch.float16 if half else BF16)
-            _lib.call("b2p_cast16_tail", _p(x), _p(s16), n_s, n_s + tail, int(half), _st())
-            gemm(T, N3, IN, op(s16, 0, stride * C, True, bs1=L * C), op(wf, 0, IN, True), gi, N3, cbs1=T * N3, nz1=B,
-                 bias=bias_cat)
-            del wf
-            U16 = None if half else s16    # the bf16 copy doubles as the weight-gradient operand
-            del s16
-        elif unf_meta is not None:
-            # tap-major weight copy: W'[n][tap*C + c] = W[n][c*k + tap] for both directions
-            wperm = torch.empty(ndir * G3, IN, device=dev)
-            for d in range(ndir):
-                _lib.call("b2p_conv_weight_permute", _p(wih[d]), _p(wperm, d * G3 * IN), G3, C, ktaps, 0, _st())
-            if bf16_mode() and not _state.fwd16:
-                # bf16 operands: the tap-major unfold materialised once in bf16 (it is also the
-                # weight-gradient operand) and a bf16 copy of the permuted weight
-                U16 = torch.empty(B * T, IN, device=dev, dtype=BF16)
-                _lib.call("b2p_unfold16", _p(x), _p(U16), B, L, C, ktaps, stride, _st())
-                wperm = cast16(wperm)
-                gemm(B * T, ndir * G3, IN, op(U16, 0, IN, True), op(wperm, 0, IN, True), gi, ndir * G3, bias=bias_cat)
-            else:   # fp32 mode, or fp16 operands (forward_f16): the fp32-operand kernel rounds while staging
-                U16 = None
-                A = conv_op(x, 0, C, T, L, stride, 0, C * ktaps, L * C, True)
-                A.conv_Cg = C  # inner j = tap*C + c
-                gemm(B * T, ndir * G3, IN, A, op(wperm, 0, IN, True), gi, ndir * G3, bias=bias_cat)
-        else:
-            _chk(x, "gru.x")
-            wperm = U16 = None
-            if bf16_mode() and IN % 8 == 0:
-                # both directions' projections as ONE GEMM over the stacked 16-bit W_ih (fp16 under
-                # forward_f16), N = ndir * 3H
-                half = _state.fwd16
-                w16 = torch.empty(ndir * G3, IN, device=dev, dtype=torch.float16 if half else BF16)
-                for d in range(ndir):
-                    _lib.call("b2p_cast16_2d", _p(wih[d]), G3, IN, IN, _p(w16, d * G3 * IN), IN, int(half), _st())
-                x16 = torch.empty(B * T, IN, device=dev, dtype=w16.dtype)
-                _lib.call("b2p_cast16_2d", _p(x), B * T, IN, IN, _p(x16), IN, int(half), _st())
-                gemm(B * T, ndir * G3, IN, op(x16, 0, IN, True), op(w16, 0, IN, True), gi, ndir * G3, bias=bias_cat)
-                del w16, x16
-            else:
-                for d in range(ndir):
-                    gemm(B * T, G3, IN, op(x, 0, IN, True), op(wih[d], 0, IN, True), gi, ndir * G3, c_off=d * G3,
-                         bias=None if bias_cat is None else _view_off(bias_cat, d * G3))
+        proj = _ImplicitUnfoldProj if implicit else _DenseProj if unf_meta is None else _UnfoldProj
+        kept = proj.forward(x, wih, bias_cat, gi, s, ctx.needs_input_grad[0])
+        # 3. recurrence
         out = torch.empty(B, T, ndir * H, device=dev)
-        saved = None if use16 else torch.empty(B, T, ndir, 4, H, device=dev)
+        saved = None if rec == "gru16" else torch.empty(B, T, ndir, 4, H, device=dev)
         if h0 is not None:
             _chk(h0, "gru.h0")
-        if use16:
-            # lane-native per-step layouts (csrc/gru16.hip): gi -> giL, kernel, hL -> out
-            giL = torch.empty(_ln_floats(B, T, H, ndir, 3), device=dev)
+        hL = None
+        if rec == "gru16":
+            # prepare: gi -> the lane-native per-step layout (csrc/gru16.hip)
+            giL = torch.empty(_ln_floats(s, 3), device=dev)
             _lib.call("b2p_gru_lane_permute", _p(gi), _p(giL), B, T, H, ndir, 3, 3, 0x210, 1, _st())
             del gi
-            hL = torch.empty(_ln_floats(B, T, H, ndir, 1), device=dev)
-            saved = torch.empty(_ln_floats(B, T, H, ndir, 4), device=dev)
-            _lib.call("b2p_gru_fwd16", _p(giL), _p(whh_s), _p(bhh_s), _p(h0), _p(hL), _p(saved), B, T, H, ndir,
-                      _st())
+            # launch
+            hL = torch.empty(_ln_floats(s, 1), device=dev)
+            saved = torch.empty(_ln_floats(s, 4), device=dev)
+            _lib.call("b2p_gru_fwd16", _p(giL), _p(whh_s), _p(bhh_s), _p(h0), _p(hL), _p(saved), B, T, H, ndir, _st())
             del giL
+            # unpack: hL -> out
             _lib.call("b2p_gru_lane_permute", _p(hL), _p(out), B, T, H, ndir, 1, 1, 0x0, 0, _st())
-        elif usemc:
-            hL = None
-            ws = _gru_mc_ws(B, H, ndir, dev)
-            _lib.call("b2p_gru_fwd_mc", _p(gi), _p(whh_s), _p(bhh_s), _p(h0), _p(out), _p(saved), _p(ws), B, T, H,
-                      ndir, _st())
-            _gru_mc_fold(ws, 1, whh[0], H, dev)
-        elif use32:
-            hL = None
-            ws = _gru32_ws(B, H, ndir, dev)
-            _lib.call("b2p_gru_fwd32", _p(gi), _p(whh_s), _p(bhh_s), _p(h0), _p(out), _p(saved), _p(ws), B, T, H,
-                      ndir, _st())
-            _gru_mc_fold(ws, 3, whh[0], H, dev)
         else:
-            hL = None
-            _lib.call("b2p_gru_fwd", _p(gi), _p(whh_s), _p(bhh_s), _p(h0), _p(out), _p(saved), B, T, H, ndir,
-                      _st())
-        ctx.save_for_backward(x, out, saved, whh_s, h0, wperm, hL, U16, *wih)
-        ctx.meta = (unf_meta, H, ndir, B, T, IN, bih[0] is not None, bhh[0] is not None, use16, usemc, use32)
-        ctx.implicit = unf_meta is not None and implicit
-        ctx.whh0 = whh[0]
+            buf = _gru_launch(rec, False, (gi, whh_s, bhh_s, h0, out, saved), s, whh[0])  # noqa: F841 (held)
+        ctx.save_for_backward(x, out, saved, whh_s, h0, hL, *wih, *kept)
+        ctx.shape, ctx.recurrence, ctx.proj = s, rec, proj
+        ctx.has_bih, ctx.has_bhh, ctx.whh0 = bih[0] is not None, bhh[0] is not None, whh[0]
+        ctx.meta = (rec == "gru16", rec == "mc", rec == "gru32")   # the choice as flags (tests/test_gru32_gpu.py)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, out, saved, whh_s, h0, wperm, hL, U16, *wih = ctx.saved_tensors
-        unf_meta, H, ndir, B, T, IN, has_bih, has_bhh, use16, usemc, use32 = ctx.meta
-        if not use16 and _GRUMC_BWD[0] is not None:
-            usemc = _GRUMC_BWD[0] and bool(_lib.load().b2p_gru_mc_supported(H))
-            use32 = use32 and not usemc
-        dev = out.device
+        x, out, saved, whh_s, h0, hL, *rest = ctx.saved_tensors
+        s = ctx.shape
+        B, T, H, G3, ndir, dev = s.B, s.T, s.H, s.G3, s.ndir, s.dev
+        wih, kept = rest[:ndir], rest[ndir:]
+        rec = _gru_recurrence_bwd(ctx.recurrence, H)
         dout = dout.contiguous()
-        G3 = 3 * H
         dgi = torch.empty(B, T, ndir * G3, device=dev)
         dgh = torch.empty(B, T, ndir * G3, device=dev)
         dh0 = torch.empty(ndir, B, H, device=dev) if (h0 is not None and ctx.needs_input_grad[4]) else None
-        if use16:
-            doL = torch.empty(_ln_floats(B, T, H, ndir, 1), device=dev)
+        # 3. recurrence; the frozen-parameter gradient GEMMs fill the chip beside its few CUs
+        if rec == "gru16":
+            # prepare: dout -> lane-native
+            doL = torch.empty(_ln_floats(s, 1), device=dev)
             _lib.call("b2p_gru_lane_permute", _p(dout), _p(doL), B, T, H, ndir, 1, 1, 0x0, 1, _st())
-            dgL = torch.empty(_ln_floats(B, T, H, ndir, 4), device=dev)
-            # frozen-parameter gradient GEMMs fill the chip beside the 4-CU recurrence
+            # launch
+            dgL = torch.empty(_ln_floats(s, 4), device=dev)
             _gru_bwd_launch(lambda: _lib.call("b2p_gru_bwd16", _p(doL), _p(whh_s), _p(hL), _p(saved), _p(h0), _p(dgL),
                                               _p(dh0), B, T, H, ndir, _st()))
             del doL
-            # dgi = LN records (0, 1, 2), dgh = LN records (0, 1, 3)
+            # unpack: dgi = LN records (0, 1, 2), dgh = LN records (0, 1, 3)
             _lib.call("b2p_gru_lane_permute", _p(dgL), _p(dgi), B, T, H, ndir, 4, 3, 0xF210, 0, _st())
             _lib.call("b2p_gru_lane_permute", _p(dgL), _p(dgh), B, T, H, ndir, 4, 3, 0x2F10, 0, _st())
             del dgL
-        elif usemc:
-            ws = _gru_mc_ws(B, H, ndir, dev)
-            # frozen-parameter gradient GEMMs beside the (H/64 x 4)-CU recurrence
-            _gru_bwd_launch(lambda: _lib.call("b2p_gru_bwd_mc", _p(dout), _p(whh_s), _p(out), _p(saved), _p(h0),
-                                              _p(dgi), _p(dgh), _p(dh0), _p(ws), B, T, H, ndir, _st()))
-            _gru_mc_fold(ws, 2, ctx.whh0, H, dev)
-        elif use32:
-            ws = _gru32_ws(B, H, ndir, dev)
-            # frozen-parameter gradient GEMMs beside the (H/32 per recurrence, at most 128)-CU recurrence
-            _gru_bwd_launch(lambda: _lib.call("b2p_gru_bwd32", _p(dout), _p(whh_s), _p(out), _p(saved), _p(h0),
-                                              _p(dgi), _p(dgh), _p(dh0), _p(ws), B, T, H, ndir, _st()))
-            _gru_mc_fold(ws, 4, ctx.whh0, H, dev)
         else:
-            dhbuf = torch.empty(ndir, B, H, device=dev)
-            _gru_bwd_launch(lambda: _lib.call("b2p_gru_bwd", _p(dout), _p(whh_s), _p(out), _p(saved), _p(h0), _p(dgi),
-                                              _p(dgh), _p(dh0), _p(dhbuf), B, T, H, ndir, _st()))
+            buf = _gru_launch(rec, True, (dout, whh_s, out, saved, h0, dgi, dgh, dh0), s, ctx.whh0)  # noqa: F841
         grads = [None] * (4 * ndir)
-        # recurrent weights: dW_hh[d] = dgh[:, :, d]^T @ hprev[d]
+        # 4. recurrent weights: dW_hh[d] = dgh[:, :, d]^T @ hprev[d]; biases: column sums
         hp = torch.empty(ndir, B, T, H, device=dev)
         _lib.call("b2p_gru_hprev", _p(out), _p(h0), _p(hp), B, T, H, ndir, _st())
         for d in range(ndir):
@@ -1835,75 +1939,13 @@ class _GRULayer(torch.autograd.Function):
                 dwhh = torch.empty(G3, H, device=dev)
                 gemm(G3, H, B * T, op(dgh, d * G3, ndir * G3, False), op(hp, d * B * T * H, H, False), dwhh, H)
                 grads[4 * d + 1] = dwhh
-            if has_bhh and ctx.needs_input_grad[5 + 4 * d + 3]:
-                db = torch.empty(G3, device=dev)
-                colsum(_view_off(dgh, d * G3), B * T, G3, db, ld=ndir * G3)
-                grads[4 * d + 3] = db
-            if has_bih and ctx.needs_input_grad[5 + 4 * d + 2]:
-                db = torch.empty(G3, device=dev)
-                colsum(_view_off(dgi, d * G3), B * T, G3, db, ld=ndir * G3)
-                grads[4 * d + 2] = db
-        dx = None
-        if ctx.implicit:
-            # dgi in the padded row layout (k/s - 1 zero rows in front, L/s rows per sample, rows t >= T
-            # zero): the weight gradient reads it as the k-major A operand, the input gradient as the
-            # overlapping-row view (one GEMM straight into dx, no col2im)
-            ktaps, stride = unf_meta
-            _, L, C = x.shape
-            R, lead, N3 = L // stride, ktaps // stride - 1, ndir * G3
-            dgp = torch.empty((lead + B * R) * N3, device=dev, dtype=BF16)
-            _lib.call("b2p_pad_rows16", _p(dgi), _p(dgp), B, T, N3, R, lead, _st())
-            if any(ctx.needs_input_grad[5 + 4 * d] for d in range(ndir)):
-                s16b = U16
-                if s16b is None:
-                    n_s, tail = B * L * C, (ktaps - stride) * C
-                    s16b = torch.empty(n_s + tail, device=dev, dtype=BF16)
-                    _lib.call("b2p_cast16_tail", _p(x), _p(s16b), n_s, n_s + tail, 0, _st())
-                dwp = torch.empty(N3, IN, device=dev)
-                gemm(N3, IN, B * R, op(dgp, lead * N3, N3, False), op(s16b, 0, stride * C, False), dwp, IN)
-                del s16b
-                for d in range(ndir):
-                    dw = torch.empty(G3, IN, device=dev)
-                    _lib.call("b2p_conv_weight_permute", _p(dwp, d * G3 * IN), _p(dw), G3, C, ktaps, 1, _st())
-                    grads[4 * d] = dw
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty(B, L, C, device=dev)
-                gemm(B * R, stride * C, (ktaps // stride) * N3, op(dgp, 0, N3, True), op(wperm, 0, stride * C, False),
-                     dx, stride * C)
-        elif unf_meta is not None:
-            ktaps, stride = unf_meta
-            _, L, C = x.shape
-            dgi16 = cast16(dgi) if U16 is not None else None
-            if any(ctx.needs_input_grad[5 + 4 * d] for d in range(ndir)):
-                dwp = torch.empty(ndir * G3, IN, device=dev)
-                if U16 is not None:
-                    gemm(ndir * G3, IN, B * T, op(dgi16, 0, ndir * G3, False), op(U16, 0, IN, False), dwp, IN)
-                else:
-                    Bop = conv_op(x, 0, C, T, L, stride, 0, C, L * C, False)
-                    gemm(ndir * G3, IN, B * T, op(dgi, 0, ndir * G3, False), Bop, dwp, IN)
-                for d in range(ndir):
-                    dw = torch.empty(G3, IN, device=dev)
-                    _lib.call("b2p_conv_weight_permute", _p(dwp, d * G3 * IN), _p(dw), G3, C, ktaps, 1, _st())
-                    grads[4 * d] = dw
-            if ctx.needs_input_grad[0]:
-                dA = torch.empty(B * T, IN, device=dev)
-                if U16 is not None:
-                    gemm(B * T, IN, ndir * G3, op(dgi16, 0, ndir * G3, True), op(wperm, 0, IN, False), dA, IN)
-                else:
-                    gemm(B * T, IN, ndir * G3, op(dgi, 0, ndir * G3, True), op(wperm, 0, IN, False), dA, IN)
-                dx = torch.empty(B, L, C, device=dev)
-                _lib.call("b2p_unfold_col2im", _p(dA), None, _p(dx), B, L, C, T, ktaps, stride, _st())
-        else:
-            for d in range(ndir):
-                if ctx.needs_input_grad[5 + 4 * d]:
-                    dw = torch.empty(G3, IN, device=dev)
-                    gemm(G3, IN, B * T, op(dgi, d * G3, ndir * G3, False), op(x, 0, IN, False), dw, IN)
-                    grads[4 * d] = dw
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty(B, T, IN, device=dev)
-                for d in range(ndir):
-                    gemm(B * T, IN, G3, op(dgi, d * G3, ndir * G3, True), op(wih[d], 0, IN, False), dx, IN,
-                         beta=0.0 if d == 0 else 1.0)
+            for k, dg, has in ((3, dgh, ctx.has_bhh), (2, dgi, ctx.has_bih)):
+                if has and ctx.needs_input_grad[5 + 4 * d + k]:
+                    grads[4 * d + k] = torch.empty(G3, device=dev)
+                    colsum(_view_off(dg, d * G3), B * T, G3, grads[4 * d + k], ld=ndir * G3)
+        # 5. projection backward
+        dx, grads[0::4] = ctx.proj.backward(dgi, x, wih, kept, s, ctx.needs_input_grad[0],
+                                            [ctx.needs_input_grad[5 + 4 * d] for d in range(ndir)])
         return (dx, None, None, None, dh0, *grads)
 
 
@@ -1917,8 +1959,7 @@ class _OffsetView:
         return self.t.data_ptr() + 4 * self.off
 
 
-def _view_off(t, off):
-    return _OffsetView(t, off)
+_view_off = _OffsetView
 
 
 def gru_layer(x, H, ndir, weights, h0=None):
@@ -1926,9 +1967,7 @@ def gru_layer(x, H, ndir, weights, h0=None):
     x: (B,T,IN) tensor or Unfolded; weights: [w_ih, w_hh, b_ih, b_hh] per direction.
     In the bf16x3 mode with the 'gru1' form (the Trainer policy, X3_POLICY_FORMS) the layer runs as in the
     bf16 mode (persistent MFMA recurrences, fp16 forward operands) and its backward follows it
-    (_prec_follow: block 'gru'), instead of the fp32 operators' recurrence kernels. Those are the persistent
-    exact-fp32 kernels (csrc/gru32.hip) in the modes of GRU32_MODES (bf16x3) for H = 256 / 512 under
-    persistent_gru32(), else one kernel per time step (csrc/gru.hip)."""
+    (_prec_follow: block 'gru'). _gru_recurrence picks the recurrence kernels."""
     with _fp32_if("gru"):
         ctxm = precision("bf16") if (_state.prec == 3 and "gru1" in (_state.x3forms or ())) else contextlib.nullcontext()
         with ctxm:
@@ -2568,18 +2607,6 @@ def attn_keep_plan_cfg(cfg, brain_encoder, inputs, training):
     T = brain_encoder.output_length(shp[1]) if hasattr(brain_encoder, "output_length") else shp[1]
     return attn_keep_plan(cfg.num_hidden_layers, shp[0], T, cfg.num_attention_heads,
                           cfg.hidden_size // cfg.num_attention_heads, cfg.attention_dropout, training)
-
-
-def _gru_bwd_launch(launch) -> None:
-    """Launch a GRU recurrence backward (launch() on the current stream) with the frozen weight
-    gradients flushed beside it (flush_wgrad): after the recurrence launch, ordered after the event
-    before it. Flushed before the launch, or with the recurrence on a stream of its own, the step times
-    measured equal (base 14.49 / 14.49 / 14.47 ms, Conformer 66.11 / - / 65.96 ms:
-    profiles/r05ak_gru_bwd_mode_ab.txt)."""
-    ev = torch.cuda.Event()
-    ev.record()
-    launch()
-    flush_wgrad(ev)
 
 
 def _keep_take(B, T, nh, p_attn):
