@@ -472,14 +472,20 @@ int b2p_gru_hprev(const float* out, const float* h0, float* hp, int64_t B, int64
 
 /* ------------------------------------------------------------------ multi-CU persistent GRU (bf16)
  * csrc/grumc.hip: the whole recurrence of an nn.GRU layer in one launch for hidden sizes one CU
- * cannot hold (256, 384, 512; the Conformer experiment's H = 512 encoder, reference
- * src/model/brain_feature_extractor.py:39-47). H/64 workgroups per (direction, 16 batch rows), each
- * keeping its units' W_hh rows in registers, exchange the state every step through L2 as tagged
- * granules. Same tensors and layouts as b2p_gru_fwd / b2p_gru_bwd (standard (B, T, ...) layouts);
+ * cannot hold (256, 384, 512, 1024; the Conformer experiment's H = 512 encoder, reference
+ * src/model/brain_feature_extractor.py:39-47, and the H = 1024 of the reference's sweeps). H/64
+ * workgroups per (direction, 16 batch rows), each keeping its units' W_hh rows in registers (at H = 1024
+ * in VGPRs, AGPRs and a last part in LDS), exchange the state every step through L2 as tagged granules. Same tensors and layouts as b2p_gru_fwd / b2p_gru_bwd (standard (B, T, ...) layouts);
  * bf16 MFMA operands, fp32 accumulation and state. workspace: b2p_gru_mc_workspace(B, H, ndir)
  * bytes, 16-byte aligned, zeroed by the call itself (the first int is a timeout flag: nonzero after
  * the call means a member never arrived; the second counts the recurrences whose members all ran
- * on one XCD and exchanged through its L2). Needs (H/64) * ndir * ceil(B/16) co-resident CUs. */
+ * on one XCD and exchanged through its L2). H <= 512: one launch, which needs (H/64) * ndir * ceil(B/16)
+ * co-resident CUs (at most 256 and at most 32 recurrences, else an argument error); workspace =
+ * 16 + 32*16*8 + ndir * ceil(B/16) * 2 * (H/64) * 1024 * 8 bytes. H = 1024 (16 workgroups per recurrence):
+ * any B; successive launches on the stream over disjoint 16-row batch groups, both directions of a group
+ * in one launch, at most 128 workgroups each (128 / 16 / ndir batch groups: B <= 64 bidirectional or B <= 128
+ * one-directional is a single launch), each recurrence on its own part of the workspace, one timeout
+ * flag for all of them; workspace = 16 + G*16*8 + G * 2 * 16 * 1024 * 8 bytes, G = ndir * ceil(B/16). */
 int b2p_gru_mc_supported(int64_t H);
 int64_t b2p_gru_mc_workspace(int64_t B, int64_t H, int ndir);
 int b2p_gru_fwd_mc(const float* gi, const float* whh, const float* bhh, const float* h0, float* out,

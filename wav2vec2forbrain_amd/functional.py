@@ -1539,7 +1539,8 @@ class Unfolded:
 # with the standard layouts (_GRU_BACKENDS) "step" one fp32 launch per time step (csrc/gru.hip), "mc" multi-CU
 # persistent 16-bit (csrc/grumc.hip), "gru32" multi-CU persistent exact fp32 (csrc/gru32.hip). _gru_recurrence
 # alone chooses (table: DESIGN.md section 5); the switches are for A/B checks.
-# hidden sizes one CU cannot hold (Conformer H = 512) take "mc" in bf16 mode (False: "step"; tools/traj_err.py)
+# hidden sizes one CU cannot hold (Conformer H = 512; 384, 1024) take "mc" in bf16 mode (False: "step";
+# tools/traj_err.py)
 _GRUMC = [True]
 # diagnostic (tools/traj_err.py): None = the backward follows the forward's choice; True / False force
 # the multi-CU / per-step fp32 backward recurrence (same saved layout)
@@ -1617,7 +1618,7 @@ def _gru_mc_fold(ws, kind, whh0, H, dev):
     if st is None:
         st = _GRU_STATUS[dev] = torch.zeros(1, dtype=torch.int32, device=dev)
     n = _GRU_LAYERS.setdefault(id(whh0), len(_GRU_LAYERS))
-    code = kind * 65536 + (n % 4096) * 16 + {256: 1, 384: 2, 512: 3}.get(H, 0)
+    code = kind * 65536 + (n % 4096) * 16 + {256: 1, 384: 2, 512: 3, 1024: 4}.get(H, 0)
     _lib.call("b2p_gru_mc_status", _p(ws), _p(st), code, _st())
 
 
@@ -1625,7 +1626,7 @@ def _gru_status_error(code: int) -> RuntimeError:
     kinds = {k: be.label + word for be in _GRU_BACKENDS.values()
              for k, word in zip(be.kinds, ("forward", "backward")) if k}
     kind = kinds.get(code // 65536, "?")
-    n, h = (code % 65536) // 16, {1: 256, 2: 384, 3: 512}.get(code % 16, "?")
+    n, h = (code % 65536) // 16, {1: 256, 2: 384, 3: 512, 4: 1024}.get(code % 16, "?")
     return RuntimeError(f"multi-CU GRU recurrence timed out ({kind} of GRU layer {n}, H={h}; recurrence id "
                         f"{code}): a member workgroup never published its state (not co-resident?), so the "
                         "layer's outputs / gradients of that step are invalid")
