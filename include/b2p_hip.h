@@ -635,6 +635,34 @@ int b2p_attn32_bwd(const float* qkv, const float* dO, const float* lse2, float* 
                    int64_t B, int64_t T, int64_t nh, int64_t dh, float scale, float drop_p, uint64_t drop_seed,
                    b2p_stream_t stream);
 
+/* The long class of the same operator: head size 64 and 257 <= T <= 512 (b2p_attn32_long_supported), the
+ * window range b2p_attn16_* covers in the bf16 mode. Semantics, layouts, the dropout mask, the seed epoch and
+ * the LayerDrop gate are exactly b2p_attn32_fwd / _bwd's above; the argument lists are the same, and delta_ws
+ * is again 2*B*nh*T floats, the same two [B][nh][T] planes (sum_key P_d dP_d; 1 / row sum of the recomputed
+ * probabilities), written by the dQ kernel and read by the dK/dV kernel.
+ * A 512-row fp32 image is 128 KB of a CU's 160 KB, so K and V (backward: Q and dO) are staged as two 256-row
+ * chunks into the same two 64 KB images, one after the other; only the 32-row tile pairs with a row < T are
+ * staged and visited.
+ *   fwd:   online softmax over the two chunks (running max and sum per query, the O accumulators rescaled by
+ *          exp2(m_old - m_new), divided by the sum at the store). lse2 = max * scale * log2e + log2(sum).
+ *   dQ:    launched first. delta over ALL keys is needed before any dS, so the chunks are swept twice: chunks
+ *          0, 1 form delta and the row sum from the recomputed P = exp2(s - lse2) and dP (the 256 class's
+ *          property: P is divided by its own row sum), chunks 1 (still staged), 0 form dQ: three stagings, the
+ *          score and dP tiles computed twice.
+ *   dK/dV: the key on the lane, the accumulators kept across the two chunks of Q and dO; the row constants
+ *          of all T queries (3 x 512 floats) sit in LDS beside the images (134 KB).
+ * Grids as above: one workgroup per (batch, head, 128 queries) for fwd and dQ, per (batch, head, 128 keys) for
+ * dK/dV. Every element of O, lse2, delta_ws and dqkv is written exactly once per launch, without atomics: runs
+ * repeat bit for bit. Stream-ordered, capturable, no allocation, no scratch. NULL pointers, dh != 64, T outside
+ * [257, 512], nh <= 0, drop_p outside [0, 1) and B*nh*T*TP >= 2^32 are rejected before any HIP call, each with
+ * a message naming the bound; B <= 0 returns 0. */
+int b2p_attn32_long_supported(int64_t T, int64_t dh);     /* 1: dh == 64 and 257 <= T <= 512 */
+int b2p_attn32_long_fwd(const float* qkv, float* O, float* lse2, int64_t B, int64_t T, int64_t nh, int64_t dh,
+                        float scale, float drop_p, uint64_t drop_seed, b2p_stream_t stream);
+int b2p_attn32_long_bwd(const float* qkv, const float* dO, const float* lse2, float* delta_ws, float* dqkv,
+                        int64_t B, int64_t T, int64_t nh, int64_t dh, float scale, float drop_p,
+                        uint64_t drop_seed, b2p_stream_t stream);
+
 /* ------------------------------------------------------------------ CTC
  * log_softmax + nn.CTCLoss(blank=0, reduction="mean", zero_infinity=True)
  * (src/model/w2v_custom_feat_extractor.py:59, 81-90). logits (B, T, C) batch-first; targets

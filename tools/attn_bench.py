@@ -2,8 +2,9 @@
 usage: python tools/attn_bench.py [--parts] [B] [T] [nh]
 --parts: also the backward that leaves the Q/K/V bias gradients as per-tile partial sums and writes no fp32
 dqkv image (b2p_attn16_bwd_parts), beside the backward with the image plus the column sum that read it.
-usage: python tools/attn_bench.py --fp32
-the fp32 / bf16x3 modes' attention core: fused exact-fp32 kernels against the unfused GEMMs + softmax."""
+usage: python tools/attn_bench.py --fp32 [B T nh]
+the fp32 / bf16x3 modes' attention core: fused exact-fp32 kernels (both shape classes) against the unfused GEMMs +
+softmax, at the given shape or at the default list."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,13 +25,17 @@ def timeit(f, n=10):
     return e0.elapsed_time(e1) / n * 1e3
 
 
-def fp32_ab():
+FP32_SHAPES = ((32, 249, 12), (8, 249, 16),                   # the 256 class: base, Conformer-large fine-tune
+               (8, 313, 16), (8, 512, 16), (32, 313, 12))     # the long class: 1,280-bin windows, the limit, base
+
+
+def fp32_ab(shapes=FP32_SHAPES):
     """--fp32: the fp32 / bf16x3 modes' attention core, fused (csrc/attn32.hip) against unfused (6 batched GEMMs +
     2 softmax kernels, functional.fused_attn32(False)), forward and backward, at the base and the Conformer-large
-    fine-tune shapes, in both modes; and the bytes each form keeps for the backward."""
+    fine-tune shapes of both shape classes, in both modes; and the bytes each form keeps for the backward."""
     dh = 64
     Fn.ATTN32_MODES = (1, 3)   # the kernels against the fp32 mode's unfused form too (its default stays unfused)
-    for B, T, nh in ((32, 249, 12), (8, 249, 16)):
+    for B, T, nh in shapes:
         qkv = torch.randn(B * T, 3 * nh * dh, device="cuda") * 0.5
         dO = torch.randn(B * T, nh * dh, device="cuda")
         for mode in ("fp32", "bf16x3"):
@@ -55,7 +60,10 @@ def fp32_ab():
 
 
 if "--fp32" in sys.argv:
-    fp32_ab()
+    shape = [int(a) for a in sys.argv[1:] if a != "--fp32"]
+    if shape and len(shape) != 3:
+        sys.exit("usage: python tools/attn_bench.py --fp32 [B T nh]")
+    fp32_ab((tuple(shape),) if shape else FP32_SHAPES)
     sys.exit(0)
 PARTS = "--parts" in sys.argv
 argv = [a for a in sys.argv[1:] if a != "--parts"]

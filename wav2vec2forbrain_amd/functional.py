@@ -2439,9 +2439,9 @@ ATTN32_MODES = (3,)
 @contextlib.contextmanager
 def fused_attn32(on: bool = True):
     """Whether the attention cores issued inside, in the modes of ATTN32_MODES (bf16x3), take the fused
-    exact-fp32 kernels (csrc/attn32.hip; the default) or the unfused batched GEMMs + softmax (tests and
-    tools/attn_bench.py run both forms in one process). The backward follows what its forward saved, not
-    this switch."""
+    exact-fp32 kernels (csrc/attn32.hip, both shape classes; the default) or the unfused batched GEMMs +
+    softmax (tests and tools/attn_bench.py run both forms in one process). The backward follows what its
+    forward saved, not this switch."""
     old = _FUSED_ATTN32[0]
     _FUSED_ATTN32[0] = bool(on)
     try:
@@ -2451,23 +2451,33 @@ def fused_attn32(on: bool = True):
 
 
 def attn32_ok(T, dh) -> bool:
-    """The fused exact-fp32 attention kernels (csrc/attn32.hip, mirrors b2p_attn32_supported) cover head size 64 and
-    1 <= T' <= 256: K and V of one head as fp32 images are 2 x 64 KB of LDS."""
+    """The 256 class of the fused exact-fp32 attention kernels (csrc/attn32.hip, mirrors b2p_attn32_supported):
+    head size 64 and 1 <= T' <= 256, K and V of one head as fp32 images are 2 x 64 KB of LDS. Longer windows,
+    up to T' = 512, are attn32_long_ok's."""
     return dh == 64 and 1 <= T <= 256
+
+
+def attn32_long_ok(T, dh) -> bool:
+    """The long class of the fused exact-fp32 attention kernels (csrc/attn32.hip, mirrors
+    b2p_attn32_long_supported): head size 64 and 257 <= T' <= 512 (windows of 1,053 to 2,080 bins), K and V
+    staged as two 256-row chunks. With attn32_ok, the window range attn16_ok has in the bf16 mode."""
+    return dh == 64 and 257 <= T <= 512
 
 
 def _attn_core_fwd(qkv, B, T, nh, dh, p_attn, seed, want16=False):
     """returns (P, Pd, O) of the unfused form, or (lse2, None, O) of the fused exact-fp32 form: taken in the
-    modes of ATTN32_MODES (bf16x3) for attn32_ok shapes under fused_attn32() when no 16-bit copy of O is wanted. The
-    fused kernels run every product on the exact fp32-operand MFMA and ignore the bf16x3 role forms
+    modes of ATTN32_MODES (bf16x3) for attn32_ok / attn32_long_ok shapes under fused_attn32() when no 16-bit
+    copy of O is wanted. The fused kernels run every product on the exact fp32-operand MFMA and ignore the bf16x3 role forms
     (x3_forms, B2P_X3_POLICY, DIAG_SWITCHES): they are at least as precise as any form the unfused GEMMs run
     under. lse2 is (B, nh, T), where P would be 4-D: _attn_core_bwd tells the forms apart by that."""
     D = nh * dh
     dev = qkv.device
-    if _state.prec in ATTN32_MODES and not want16 and _FUSED_ATTN32[0] and attn32_ok(T, dh):
+    if (_state.prec in ATTN32_MODES and not want16 and _FUSED_ATTN32[0]
+            and (attn32_ok(T, dh) or attn32_long_ok(T, dh))):
         O = torch.empty(B * T, D, device=dev)
         lse2 = torch.empty(B, nh, T, device=dev)
-        _lib.call("b2p_attn32_fwd", _p(qkv), _p(O), _p(lse2), B, T, nh, dh, dh ** -0.5, float(p_attn), seed, _st())
+        fwd = "b2p_attn32_long_fwd" if attn32_long_ok(T, dh) else "b2p_attn32_fwd"
+        _lib.call(fwd, _p(qkv), _p(O), _p(lse2), B, T, nh, dh, dh ** -0.5, float(p_attn), seed, _st())
         return lse2, None, O
     Tp = (T + 3) // 4 * 4
     S = torch.empty(B, nh, T, Tp, device=dev)
@@ -2488,15 +2498,16 @@ def _attn_core_fwd(qkv, B, T, nh, dh, p_attn, seed, want16=False):
 
 def _attn_core_bwd(qkv, P, Pd, dO, B, T, nh, dh, p_attn, seed, want16=False):
     """returns dqkv (B*T, 3D) = [dQ | dK | dV] (and its bf16 copy when want16). A 3-D P is the fused
-    forward's lse2 (B, nh, T): the backward is then b2p_attn32_bwd whatever the mode is by now (_prec_follow
-    and the attribution switches may change it between forward and backward)."""
+    forward's lse2 (B, nh, T): the backward is then b2p_attn32_bwd (b2p_attn32_long_bwd for T' > 256) whatever the
+    mode is by now (_prec_follow and the attribution switches may change it between forward and backward)."""
     D = nh * dh
     dev = qkv.device
     if P.dim() == 3:
         assert not want16, "the fused exact-fp32 attention keeps no 16-bit copies"
         dqkv = torch.empty(B * T, 3 * D, device=dev)
         delta = torch.empty(2, B, nh, T, device=dev)   # delta, 1 / row sum (b2p_hip.h)
-        _lib.call("b2p_attn32_bwd", _p(qkv), _p(dO), _p(P), _p(delta), _p(dqkv), B, T, nh, dh, dh ** -0.5,
+        bwd = "b2p_attn32_long_bwd" if attn32_long_ok(T, dh) else "b2p_attn32_bwd"
+        _lib.call(bwd, _p(qkv), _p(dO), _p(P), _p(delta), _p(dqkv), B, T, nh, dh, dh ** -0.5,
                   float(p_attn), seed, _st())
         return dqkv
     Tp = P.shape[-1]
@@ -2526,7 +2537,8 @@ def _attn_core_bwd(qkv, P, Pd, dO, B, T, nh, dh, p_attn, seed, want16=False):
 def attn16_ok(T, dh) -> bool:
     """The fused bf16 attention kernels (csrc/attn16.hip) cover head size 64 and T' <= 512 (windows of up
     to 2,080 bins; the 256-key class keeps the dropout keep bits for the backward, the 512-key class
-    rehashes them)."""
+    rehashes them). The bf16x3 mode's exact-fp32 kernels cover the same range in their own two classes
+    (attn32_ok, attn32_long_ok)."""
     return dh == 64 and 0 < T <= 512
 
 
