@@ -626,8 +626,9 @@ int b2p_attn16_bwd_parts(int qkv_fp16, const void* qkv16, const void* dO16, cons
  * fwd and the dQ kernel run one workgroup per (batch, head, 128 queries), the dK/dV kernel one per (batch,
  * head, 128 keys). Rows >= T of the last block are neither computed into outputs nor stored; every element
  * of O, lse2, delta_ws and dqkv is written exactly once per launch, without atomics, so runs repeat bit for
- * bit. Stream-ordered, capturable, no allocation. NULL pointers, dh != 64, T outside [1, 256] and the
- * 2^32 bound are rejected before any HIP call; B <= 0 returns 0. */
+ * bit. Stream-ordered, capturable, no allocation. NULL pointers, dh != 64, T outside [1, 256], nh <= 0, drop_p
+ * outside [0, 1) and B*nh*T*TP >= 2^32 are rejected before any HIP call (one check serves both classes and both
+ * directions); B <= 0 returns 0. */
 int b2p_attn32_supported(int64_t T, int64_t dh);          /* 1: dh == 64 and 1 <= T <= 256 */
 int b2p_attn32_fwd(const float* qkv, float* O, float* lse2, int64_t B, int64_t T, int64_t nh, int64_t dh,
                    float scale, float drop_p, uint64_t drop_seed, b2p_stream_t stream);
@@ -640,6 +641,9 @@ int b2p_attn32_bwd(const float* qkv, const float* dO, const float* lse2, float* 
  * the LayerDrop gate are exactly b2p_attn32_fwd / _bwd's above; the argument lists are the same, and delta_ws
  * is again 2*B*nh*T floats, the same two [B][nh][T] planes (sum_key P_d dP_d; 1 / row sum of the recomputed
  * probabilities), written by the dQ kernel and read by the dK/dV kernel.
+ * One kernel family serves both classes (csrc/attn32.hip): the forward and the dK/dV kernel are templates over the
+ * number of 256-row chunks (1: the class above, 2: this one), the dQ kernel has one body per class around shared
+ * pieces.
  * A 512-row fp32 image is 128 KB of a CU's 160 KB, so K and V (backward: Q and dO) are staged as two 256-row
  * chunks into the same two 64 KB images, one after the other; only the 32-row tile pairs with a row < T are
  * staged and visited.

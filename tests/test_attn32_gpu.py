@@ -13,102 +13,20 @@ The unfused path produces no lse, so lse2 (checked as ln: lse2 * ln 2) is held t
 domain, plus one v_log_f32 result and one add, stays below 4 ulp of max|ref|.
 """
 import ctypes
-import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from tests.helpers import CFG, load_fixture, build_model, batch_dict
+from tests.attn32_cases import Attn32Cases, attn_gemms as _attn_gemms, batch as _batch, fn as _fn, \
+    nan_bufs as _nan_bufs, ref64_plain as _ref64_plain, three_steps, unfused as _unfused
+from tests.helpers import CFG, load_fixture, build_model
 
 pytestmark = pytest.mark.gpu
 
-B, NH, DH = 2, 2, 64
-D = NH * DH
-SCALE = DH ** -0.5
-ULP4 = 4 * 2.0 ** -24
-SEED = 0x5EED1234
-
-
-def _fn():
-    from wav2vec2forbrain_amd import functional as Fn
-    return Fn
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(T):
-    g = torch.Generator().manual_seed(1000 + T)
-    qkv = torch.randn(B * T, 3 * D, generator=g) * 0.5
-    dO = torch.randn(B * T, D, generator=g)
-    return qkv, dO
-
-
-def _heads(x, T):   # (B*T, nh*dh) -> (B, nh, T, dh)
-    return x.view(B, T, NH, DH).permute(0, 2, 1, 3)
-
-
-def _ref64(T, keep=None, p=0.0):
-    """float64 restatement: O (B*T, D), ln-domain lse (B, nh, T), dqkv (B*T, 3D); keep: (B, nh, T, T) bool."""
-    qkv, dO = _inputs(T)
-    x = qkv.double().clone().requires_grad_(True)
-    q, k, v = (_heads(x[:, i * D:(i + 1) * D], T) for i in range(3))
-    S = q @ k.transpose(-1, -2) * SCALE
-    lse = torch.logsumexp(S, -1)
-    P = torch.softmax(S, -1)
-    if keep is not None:
-        P = P * keep.double() / (1.0 - p)
-    O = (P @ v).permute(0, 2, 1, 3).reshape(B * T, D)
-    O.backward(dO.double())
-    return O.detach(), lse.detach(), x.grad.detach()
-
-
-@functools.lru_cache(maxsize=None)
-def _ref64_plain(T):
-    return _ref64(T)
-
-
-def _fused(T, p, seed=SEED, bufs=None):
-    """O, lse2, dqkv, delta from the C entry points (into bufs when given)."""
-    Fn = _fn()
-    qkv, dO = (t.cuda() for t in _inputs(T))
-    if bufs is None:
-        bufs = _nan_bufs(T)
-    O, lse2, dqkv, delta = bufs
-    Fn._lib.call("b2p_attn32_fwd", qkv.data_ptr(), O.data_ptr(), lse2.data_ptr(), B, T, NH, DH, SCALE, p, seed, Fn._st())
-    Fn._lib.call("b2p_attn32_bwd", qkv.data_ptr(), dO.data_ptr(), lse2.data_ptr(), delta.data_ptr(), dqkv.data_ptr(),
-                 B, T, NH, DH, SCALE, p, seed, Fn._st())
-    torch.cuda.synchronize()
-    return O, lse2, dqkv, delta
-
-
-def _nan_bufs(T):
-    nan = float("nan")
-    return (torch.full((B * T, D), nan, device="cuda"), torch.full((B, NH, T), nan, device="cuda"),
-            torch.full((B * T, 3 * D), nan, device="cuda"), torch.full((2, B, NH, T), nan, device="cuda"))
-
-
-def _unfused(T, p, seed=SEED):
-    """O, dqkv, P, Pd of the unfused fp32-mode path on the same inputs."""
-    Fn = _fn()
-    qkv, dO = (t.cuda() for t in _inputs(T))
-    with Fn.precision("fp32"), Fn.fused_attn32(False):
-        P, Pd, O = Fn._attn_core_fwd(qkv, B, T, NH, DH, p, seed)
-        assert P.dim() == 4
-        dqkv = Fn._attn_core_bwd(qkv, P, Pd, dO, B, T, NH, DH, p, seed)
-    torch.cuda.synchronize()
-    return O, dqkv, P[..., :T], (P if Pd is None else Pd)[..., :T]
-
-
-def _err(x, ref):
-    return float((x.detach().double().cpu() - ref).abs().max())
-
-
-def _hold(what, T, got, unf, ref):
-    e_f, e_u, m = _err(got, ref), (0.0 if unf is None else _err(unf, ref)), float(ref.abs().max())
-    bound = 2 * e_u + ULP4 * m
-    print(f"attn32 T'={T} {what}: E_u {e_u:.3e} E_f {e_f:.3e} bound {bound:.3e} max|ref| {m:.3e}")
-    return e_f <= bound, (what, T, e_f, e_u, bound)
+_CASES = Attn32Cases("b2p_attn32_fwd", "b2p_attn32_bwd", "attn32")
+_fused, _hold, _dropout_case = _CASES.fused, _CASES.hold, _CASES.dropout_case
 
 
 @pytest.mark.timeout(120)
@@ -122,19 +40,6 @@ def test_against_float64(T):
     res = [_hold("O", T, O, Ou, Oref), _hold("dqkv", T, dqkv, du, dref),
            _hold("lse", T, lse2.double() * math.log(2.0), None, lse_ref)]
     assert all(ok for ok, _ in res), [r for ok, r in res if not ok]
-
-
-def _dropout_case(T, p):
-    Ou, du, P, Pd = _unfused(T, p)
-    assert bool((P > 0).all())          # far above fp32 underflow: Pd != 0 is the keep pattern
-    keep = (Pd != 0).cpu()
-    frac = float(keep.float().mean())
-    assert abs(frac - (1 - p)) < 0.05, frac
-    Oref, _, dref = _ref64(T, keep, p)
-    O, _, dqkv, _ = _fused(T, p)
-    res = [_hold(f"O p={p}", T, O, Ou, Oref), _hold(f"dqkv p={p}", T, dqkv, du, dref)]
-    assert all(ok for ok, _ in res), [r for ok, r in res if not ok]
-    return O
 
 
 @pytest.mark.timeout(120)
@@ -188,16 +93,6 @@ def test_layerdrop_gate():
     O, lse2, dqkv, delta = closed
     assert bool((O == 0).all()) and bool(torch.isfinite(lse2).all())
     assert bool((dqkv == 0).all()) and bool((delta == 0).all())
-
-
-def _batch(cfg):
-    from wav2vec2forbrain_amd.datasets.batch_types import make_b2t_batch
-    b = batch_dict(cfg)
-    return make_b2t_batch(b["x"], b["target"], b["day_idxs"], b["input_lens"], b["target_lens"]).cuda()
-
-
-def _attn_gemms(log, nz):
-    return [e for e in log if e["nz"] == nz]
 
 
 # The tiny fixtures (tiny_a, tiny_stable, tiny_conf) have head size 16 and keep the unfused path; the fixtures of
@@ -264,88 +159,8 @@ def test_models_take_the_fused_path_and_match_goldens(name):
 
 
 def _three_steps(graphs):
-    """One eager step, then two more steps: replays of the captured step (graphs), or eager launches of the very
-    step the capture records: the device-drawn LayerDrop form, the same host-drawn seeds and the same step
-    counter mixed into every dropout seed. Tiny Conformer with head size 64 in fp32 mode, the 0.1 training
-    dropouts (attention dropout among them), LayerDrop 0.5, Adam over the brain encoder."""
-    Fn = _fn()
-    from wav2vec2forbrain_amd.optim import HipAdam
-    from wav2vec2forbrain_amd.train.step_graph import StepGraph
-    lib = Fn._lib.load()
-    cfg = dict(CFG["tiny_conf"], name="tiny_conf_h64", hidden_size=128, heads=2)
-    model = build_model(cfg, train_dropouts=True)
-    model.train()
-    for m in model.modules():
-        if hasattr(m, "sync_metrics"):
-            m.sync_metrics = False
-    model.w2v_encoder.wav2vec2_conformer.encoder.config.layerdrop = 0.5
-    for n, q in model.named_parameters():
-        if not n.startswith("brain_encoder."):
-            q.requires_grad_(False)
-    opt = HipAdam([q for q in model.brain_encoder.parameters()], lr=1e-3)
-    batch = _batch(cfg)
-
-    def fwd_bwd():
-        opt.zero_grad()
-        out = model(batch)
-        out.loss.backward()
-        return out.metrics["ctc_loss"]
-
-    def step():
-        loss = fwd_bwd()
-        opt.step()
-        return loss
-
-    def reseed():     # the seeds the host draws while the step is captured: every replay reuses them
-        Fn.SEEDS.reseed(900)
-        Fn.LD_SEEDS.reseed(901)
-
-    Fn.SEEDS.reseed(777)
-    torch.manual_seed(779)      # the eager step's host LayerDrop draws
-    epoch = torch.zeros(1, dtype=torch.int64, device="cuda")
-    patterns = []
-    try:
-        Fn.ATTN32_MODES = (1, 3)    # the fused kernels in fp32 arithmetic (the fp32 mode's default is unfused)
-        with Fn.precision("fp32"):
-            losses = [float(step())]
-            Fn.GEMM_LOG = []            # every layer runs below (LayerDrop gates them on the device)
-            Fn.LAYERDROP_LOG = []
-            if graphs:
-                reseed()
-                sg = StepGraph(step, opt, warmup=0, warm_replays=0, epoch=epoch)
-                sg.capture()
-                for _ in range(2):
-                    losses.append(float(sg.replay()))
-                    patterns.append(tuple(Fn.layerdrop_keep(0.5, s, int(epoch.item())) for s in Fn.LAYERDROP_LOG))
-                sg.release()
-            else:
-                real = Fn.capturing
-                try:
-                    Fn._lib.check(lib.b2p_set_seed_epoch(ctypes.c_void_p(epoch.data_ptr())), "set_seed_epoch")
-                    for _ in range(2):
-                        reseed()
-                        Fn.LAYERDROP_LOG = []
-                        Fn._lib.check(lib.b2p_seed_epoch_step(ctypes.c_void_p(epoch.data_ptr()),
-                                                              ctypes.c_void_p(Fn._st())), "step")
-                        Fn.capturing = lambda: True      # the forward and backward the capture records
-                        try:
-                            loss = fwd_bwd()
-                        finally:
-                            Fn.capturing = real
-                        opt.step()
-                        losses.append(float(loss))
-                        patterns.append(tuple(Fn.layerdrop_keep(0.5, s, int(epoch.item())) for s in Fn.LAYERDROP_LOG))
-                finally:
-                    Fn.capturing = real
-                    Fn._lib.check(lib.b2p_set_seed_epoch(None), "set_seed_epoch")
-            n_attn = len(_attn_gemms(Fn.GEMM_LOG, cfg["B"] * cfg["heads"]))
-    finally:
-        Fn.GEMM_LOG = None
-        Fn.LAYERDROP_LOG = None
-        Fn.ATTN32_MODES = (3,)
-    torch.cuda.synchronize()
-    opt.sync_steps()
-    return losses, {n: q.detach().clone() for n, q in model.named_parameters()}, n_attn, patterns
+    """attn32_cases.three_steps on the tiny Conformer with head size 64 (T' <= 256)."""
+    return three_steps(dict(CFG["tiny_conf"], name="tiny_conf_h64", hidden_size=128, heads=2), graphs)
 
 
 @pytest.mark.timeout(300)

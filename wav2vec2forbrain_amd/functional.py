@@ -2464,6 +2464,16 @@ def attn32_long_ok(T, dh) -> bool:
     return dh == 64 and 257 <= T <= 512
 
 
+def _attn32_entry(T, dh):
+    """The (forward, backward) entry points of the fused exact-fp32 attention that serve (T', head size), or None:
+    the one place that maps a shape to its class."""
+    if attn32_ok(T, dh):
+        return "b2p_attn32_fwd", "b2p_attn32_bwd"
+    if attn32_long_ok(T, dh):
+        return "b2p_attn32_long_fwd", "b2p_attn32_long_bwd"
+    return None
+
+
 def _attn_core_fwd(qkv, B, T, nh, dh, p_attn, seed, want16=False):
     """returns (P, Pd, O) of the unfused form, or (lse2, None, O) of the fused exact-fp32 form: taken in the
     modes of ATTN32_MODES (bf16x3) for attn32_ok / attn32_long_ok shapes under fused_attn32() when no 16-bit
@@ -2472,12 +2482,11 @@ def _attn_core_fwd(qkv, B, T, nh, dh, p_attn, seed, want16=False):
     under. lse2 is (B, nh, T), where P would be 4-D: _attn_core_bwd tells the forms apart by that."""
     D = nh * dh
     dev = qkv.device
-    if (_state.prec in ATTN32_MODES and not want16 and _FUSED_ATTN32[0]
-            and (attn32_ok(T, dh) or attn32_long_ok(T, dh))):
+    entry = _attn32_entry(T, dh) if _state.prec in ATTN32_MODES and not want16 and _FUSED_ATTN32[0] else None
+    if entry:
         O = torch.empty(B * T, D, device=dev)
         lse2 = torch.empty(B, nh, T, device=dev)
-        fwd = "b2p_attn32_long_fwd" if attn32_long_ok(T, dh) else "b2p_attn32_fwd"
-        _lib.call(fwd, _p(qkv), _p(O), _p(lse2), B, T, nh, dh, dh ** -0.5, float(p_attn), seed, _st())
+        _lib.call(entry[0], _p(qkv), _p(O), _p(lse2), B, T, nh, dh, dh ** -0.5, float(p_attn), seed, _st())
         return lse2, None, O
     Tp = (T + 3) // 4 * 4
     S = torch.empty(B, nh, T, Tp, device=dev)
@@ -2506,8 +2515,7 @@ def _attn_core_bwd(qkv, P, Pd, dO, B, T, nh, dh, p_attn, seed, want16=False):
         assert not want16, "the fused exact-fp32 attention keeps no 16-bit copies"
         dqkv = torch.empty(B * T, 3 * D, device=dev)
         delta = torch.empty(2, B, nh, T, device=dev)   # delta, 1 / row sum (b2p_hip.h)
-        bwd = "b2p_attn32_long_bwd" if attn32_long_ok(T, dh) else "b2p_attn32_bwd"
-        _lib.call(bwd, _p(qkv), _p(dO), _p(P), _p(delta), _p(dqkv), B, T, nh, dh, dh ** -0.5,
+        _lib.call(_attn32_entry(T, dh)[1], _p(qkv), _p(dO), _p(P), _p(delta), _p(dqkv), B, T, nh, dh, dh ** -0.5,
                   float(p_attn), seed, _st())
         return dqkv
     Tp = P.shape[-1]
