@@ -511,10 +511,16 @@ int b2p_gru_mc_debug_withhold(int member);
  * 16 bits. The backward exchanges partial dh sums (each member multiplies its own W_hh rows, transposed,
  * by its own dgh; every member adds the partials of its units in member order). Deterministic.
  * Same tensors and layouts as b2p_gru_fwd / b2p_gru_bwd, so either form's backward consumes either
- * form's saved state; bhh, h0 and dh0 may be NULL. H = 256 or 512 (b2p_gru32_supported).
+ * form's saved state; bhh, h0 and dh0 may be NULL. H = 256, 512 or 1024 (b2p_gru32_supported). H = 1024 is the
+ * same kernels at P = 32 members (at best one whole XCD per recurrence) with W_hh in AGPRs, VGPRs and LDS and the
+ * exchange swept in four parts.
  * workspace: b2p_gru32_workspace(B, H, ndir) bytes (0 for an unsupported H or ndir), 16-byte aligned,
  * zeroed by the call itself before its launches; its first int is the timeout flag (b2p_gru_mc_status
- * folds it into the persistent status word), the second counts the recurrences found on one XCD.
+ * folds it into the persistent status word), the second counts the recurrences found on one XCD. Its size, with
+ * G = ndir * ceil(B/16) recurrences, P = H/32 members and S member-id words per recurrence (16; 32 at H = 1024):
+ *   16 + G * S * 8 + G * 2 * P * P * 512 * 8 bytes
+ * (fail words, ids, then per recurrence two slots of P x P x 512 granules of 8 bytes, the backward's; the forward
+ * uses 2 x P x 512 of them). At H = 1024 that is 8 MiB + 256 B per recurrence, 64 MiB at B = 64 bidirectional.
  * A launch holds at most 128 workgroups (all must be resident); ndir * ceil(B/16) * (H/32) above that
  * runs as successive launches over disjoint batch groups on the same stream. Stateless, stream-ordered,
  * capturable. NULL pointers, an unsupported H, ndir outside {1, 2} and a misaligned workspace are rejected

@@ -2,7 +2,9 @@
 (csrc/gru32.hip: b2p_gru_fwd32 / b2p_gru_bwd32) against the per-time-step kernels (csrc/gru.hip: b2p_gru_fwd /
 b2p_gru_bwd), forward and backward, both directions, through the C ABI (HIP-event time, 3 warm launches,
 median of 11). Shapes: the Conformer-large fine-tune's (B 8, T' 249, H 512) and the bench batch (B 32, T' 249,
-H 256 and 512). Also the largest difference of the two forms' outputs and the timeout flag.
+H 256 and 512). Also the largest difference of the two forms' outputs and the timeout flag. H = 1024 (P = 32
+members; B 8 / 32 / 64 at T' 249 is the measured set) has no per-step backward: the forwards are compared and the
+persistent backward is timed alone.
 --mc: the same for the bf16 mode's multi-CU persistent kernels (csrc/grumc.hip: b2p_gru_fwd_mc / b2p_gru_bwd_mc;
 H 256, 384, 512, 1024) against the per-time-step kernels.
 usage: python tools/gru_bench.py [--mc] [B T H ...]"""

@@ -47,6 +47,80 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// ---- H = 1024 (P = 32 members: at best one whole XCD per recurrence). Everything the size forces sits under
+// `H == 1024`, so the 256 / 512 instantiations compile as before.
+// A wave's W_hh values are 384 registers per lane in both passes, and a lane has 256 VGPRs + 256 AGPRs. As in
+// csrc/grumc.hip ("MFMAs that read W_hh straight from AGPRs"), the MFMAs are inline-asm statements whose A
+// operands carry an "a" constraint for the first *_A statements (they stay in AGPRs for the whole launch), "v"
+// for the next ones, and the statements from *_L on read theirs from LDS ([fragment][thread] float4: one
+// conflict-free ds_read_b128 per four values and step). Nothing inside an asm string is padded by the
+// compiler: "s_nop 1" opens every statement (a just-written operand: the accumulators' zeros, a
+// v_accvgpr_write of the prologue), an accumulator goes from one MFMA to the next only as the whole C of its
+// own chain (no wait), and the last statements of a step end with the wait of their results' way to any other
+// reader (8-pass XDL: "s_nop 15" inside the string, so that no compiler copy can come before it).
+// The exchange is swept SW1024 granules per lane at a time (sweep_parts: the sweep keeps what it polls in
+// registers, and all 64 would be 128 of them), and the members' XCC ids take a stride of their own.
+template <int H>
+constexpr int ids_stride() { return H == 1024 ? 32 : IDS_PER_GROUP; }
+constexpr int SW1024 = 16;
+template <int H>
+constexpr int sweep_width(int ngr) { return H == 1024 ? SW1024 : ngr; }
+// forward: a statement is one float4 chunk of K (4 k-steps x 3 gates, 12 A-values); 32 per step
+constexpr int FWD_A = 21;   // chunks 0..20: 252 AGPRs
+constexpr int FWD_L = 27;   // chunks 21..26: 72 VGPRs; 27..31 in LDS (15 float4 per thread, 61,440 B)
+// backward: a statement is one k-step of 8 output tiles (8 A-values); 48 per step
+constexpr int BWD_A = 30;   // statements 0..29: 240 AGPRs (the other 16 are the compiler's: with all 256 taken it
+                            // spills loop-invariant addresses to scratch)
+constexpr int BWD_L = 30;   // none in VGPRs (16 accumulators and the loop's addresses fill them); 30..47 in LDS
+                            // (36 float4 per thread, 147,456 B)
+constexpr size_t FRAG_BYTES = (size_t)NTH * 16;
+template <int H>
+constexpr size_t fwd_lds() { return H == 1024 ? (size_t)BG * (H + 4) * 4 + (32 - FWD_L) * 3 * FRAG_BYTES : 0; }
+template <int H>
+constexpr size_t bwd_lds() { return H == 1024 ? (48 - BWD_L) * 2 * FRAG_BYTES : 0; }
+static_assert(fwd_lds<1024>() + 6144 <= 163840 && bwd_lds<1024>() + 12800 <= 163840, "a CU has 160 KB of LDS");
+
+#define B2P_F32OP "v_mfma_f32_16x16x4_f32"
+// c[g] += A[g][j] . b[j] over j = 0..3, gates g = 0..2, in the order of the 256 / 512 loop (j outer, g inner)
+#define B2P_MFMA12(NAME, CA, END)                                                                                     \
+  __device__ __forceinline__ void NAME(f32x4& c0, f32x4& c1, f32x4& c2, const float* a0, const float* a1,             \
+                                       const float* a2, const float* b) {                                             \
+    asm("s_nop 1\n\t"                                                                                                 \
+        B2P_F32OP " %0, %3, %15, %0\n\t" B2P_F32OP " %1, %7, %15, %1\n\t" B2P_F32OP " %2, %11, %15, %2\n\t"            \
+        B2P_F32OP " %0, %4, %16, %0\n\t" B2P_F32OP " %1, %8, %16, %1\n\t" B2P_F32OP " %2, %12, %16, %2\n\t"            \
+        B2P_F32OP " %0, %5, %17, %0\n\t" B2P_F32OP " %1, %9, %17, %1\n\t" B2P_F32OP " %2, %13, %17, %2\n\t"            \
+        B2P_F32OP " %0, %6, %18, %0\n\t" B2P_F32OP " %1, %10, %18, %1\n\t" B2P_F32OP " %2, %14, %18, %2" END            \
+        : "+v"(c0), "+v"(c1), "+v"(c2)                                                                                \
+        : CA(a0[0]), CA(a0[1]), CA(a0[2]), CA(a0[3]), CA(a1[0]), CA(a1[1]), CA(a1[2]), CA(a1[3]), CA(a2[0]),          \
+          CA(a2[1]), CA(a2[2]), CA(a2[3]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]));                               \
+  }
+// c[i] += a[i] . b for 8 output tiles (one k-step)
+#define B2P_MFMA8(NAME, CA, END)                                                                                      \
+  __device__ __forceinline__ void NAME(f32x4* c, float a0, float a1, float a2, float a3, float a4, float a5,          \
+                                       float a6, float a7, float b) {                                                 \
+    asm("s_nop 1\n\t"                                                                                                 \
+        B2P_F32OP " %0, %8, %16, %0\n\t" B2P_F32OP " %1, %9, %16, %1\n\t" B2P_F32OP " %2, %10, %16, %2\n\t"            \
+        B2P_F32OP " %3, %11, %16, %3\n\t" B2P_F32OP " %4, %12, %16, %4\n\t" B2P_F32OP " %5, %13, %16, %5\n\t"          \
+        B2P_F32OP " %6, %14, %16, %6\n\t" B2P_F32OP " %7, %15, %16, %7" END                                            \
+        : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7])              \
+        : CA(a0), CA(a1), CA(a2), CA(a3), CA(a4), CA(a5), CA(a6), CA(a7), "v"(b));                                    \
+  }
+B2P_MFMA12(mfma12_a, "a", "")
+B2P_MFMA12(mfma12_v, "v", "")
+B2P_MFMA12(mfma12_v_last, "v", "\n\ts_nop 15")
+B2P_MFMA8(mfma8_a, "a", "")
+B2P_MFMA8(mfma8_v, "v", "")
+B2P_MFMA8(mfma8_v_last, "v", "\n\ts_nop 15")
+#undef B2P_MFMA12
+#undef B2P_MFMA8
+#undef B2P_F32OP
+// prologue: a statement's values are put in their file before the next one's loads are issued (left alone,
+// every load of the 384 comes first)
+__device__ __forceinline__ void pin_f32(float& x, bool agpr) {
+  if (agpr) asm volatile("" : "+a"(x));
+  else asm volatile("" : "+v"(x));
+}
+
 // ------------------------------------------------------------------------------------------ forward
 // exchange slots: [group][2][P * 512] granules. h_s of member m, batch row b, unit u = 16ub + 4lq + i of m sits at
 // m*512 + ((4ub + i)*4 + lq)*16 + b: the 64 lanes of one publishing store (fixed ub, i) write 512 contiguous
@@ -61,9 +135,14 @@ __global__ void __launch_bounds__(NTH, 1) gru32_fwd(const float* __restrict__ gi
   constexpr int KC = H / 32;                 // float4 chunks of this wave's K half
   constexpr int HP = H + 4;                  // floats per batch row of the h image (16-B stagger)
   constexpr int NGR = P * MGR / NTH;         // granules swept per lane
+  constexpr int SW = sweep_width<H>(NGR);    // of them per sweep call
   constexpr int G3 = 3 * H;
-  __shared__ __attribute__((aligned(16))) float himg[BG * HP];
+  constexpr bool WIDE = H == 1024;           // the h image and the W_hh chunks from FWD_L on in dynamic LDS
+  __shared__ __attribute__((aligned(16))) float himg_s[WIDE ? 4 : BG * HP];
   __shared__ __attribute__((aligned(16))) f32x4 red[2 * 3 * 64];   // upper K half's sums: [unit block][gate][lane]
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* const himg = WIDE ? reinterpret_cast<float*>(smem) : himg_s;
+  float4* const wl = reinterpret_cast<float4*>(smem + (size_t)BG * HP * 4);
 
   int d, bgl, m;
   if (!place(P, ndir * nbg, d, bgl, m, nbg)) return;
@@ -79,18 +158,36 @@ __global__ void __launch_bounds__(NTH, 1) gru32_fwd(const float* __restrict__ gi
   const int gg = d * nbg_all + bg;
   unsigned long long* xg = xch + (int64_t)gg * 2 * P * MGR;
   bool dead = false;
-  const bool local = same_xcd(ids + gg * IDS_PER_GROUP, P, m, fail, dead);
+  const bool local = same_xcd(ids + gg * ids_stride<H>(), P, m, fail, dead);
 
   // A = W_hh rows of (gate g, unit u0 + lr): k = kb + 16c + 4lq + j sits in wf[g][4c + j], the order in which
   // the h image is read as float4 (any k order does, as long as A and B agree)
   float wf[3][4 * KC];
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
+  if constexpr (WIDE) {   // chunk by chunk: into AGPRs, VGPRs or LDS
 #pragma unroll
     for (int c = 0; c < KC; ++c) {
-      const float4 v = *reinterpret_cast<const float4*>(W + (int64_t)(g * H + u0 + lr) * H + kb + 16 * c + 4 * lq);
-      wf[g][4 * c] = v.x; wf[g][4 * c + 1] = v.y; wf[g][4 * c + 2] = v.z; wf[g][4 * c + 3] = v.w;
+#pragma unroll
+      for (int g = 0; g < 3; ++g) {
+        const float4 v = *reinterpret_cast<const float4*>(W + (int64_t)(g * H + u0 + lr) * H + kb + 16 * c + 4 * lq);
+        if (c >= FWD_L) {
+          wl[((c - FWD_L) * 3 + g) * NTH + tid] = v;
+        } else {
+          wf[g][4 * c] = v.x; wf[g][4 * c + 1] = v.y; wf[g][4 * c + 2] = v.z; wf[g][4 * c + 3] = v.w;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) pin_f32(wf[g][4 * c + j], c < FWD_A);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
+  } else {
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        const float4 v = *reinterpret_cast<const float4*>(W + (int64_t)(g * H + u0 + lr) * H + kb + 16 * c + 4 * lq);
+        wf[g][4 * c] = v.x; wf[g][4 * c + 1] = v.y; wf[g][4 * c + 2] = v.z; wf[g][4 * c + 3] = v.w;
+      }
+  }
   float4 bh[3];
 #pragma unroll
   for (int g = 0; g < 3; ++g)
@@ -126,7 +223,7 @@ __global__ void __launch_bounds__(NTH, 1) gru32_fwd(const float* __restrict__ gi
     if (s > 0) {   // h_{s-1} of every member: tag s, slot (s-1) & 1. Every wave left the image at the
                    // reduction barrier of step s-1, so one image does.
       const unsigned tag = (unsigned)s;
-      sweep<NGR>(xg + ((s - 1) & 1) * P * MGR, [tag](unsigned long long x) { return (unsigned)(x >> 32) == tag; },
+      sweep_parts<NGR, SW>(xg + ((s - 1) & 1) * P * MGR, [tag](unsigned long long x) { return (unsigned)(x >> 32) == tag; },
                  [&](int q, unsigned long long x) {
                    const int uu = ((q >> 8) & 1) * 16 + ((q >> 4) & 3) * 4 + ((q >> 6) & 3);
                    himg[(q & 15) * HP + (q >> 9) * UPM + uu] = __uint_as_float((unsigned)x);
@@ -137,14 +234,35 @@ __global__ void __launch_bounds__(NTH, 1) gru32_fwd(const float* __restrict__ gi
 #pragma unroll
     for (int g = 0; g < 3; ++g) acc[g][0] = acc[g][1] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* hrow = himg + lr * HP + kb + 4 * lq;
+    if constexpr (WIDE) {
+      float4 nb = *reinterpret_cast<const float4*>(hrow);   // h is read one chunk ahead of its MFMAs
 #pragma unroll
-    for (int c = 0; c < KC; ++c) {
-      const float4 hv = *reinterpret_cast<const float4*>(hrow + 16 * c);
-      const float hk[4] = {hv.x, hv.y, hv.z, hv.w};
+      for (int c = 0; c < KC; ++c) {
+        const float4 hv = nb;
+        if (c + 1 < KC) nb = *reinterpret_cast<const float4*>(hrow + 16 * (c + 1));
+        const float hk[4] = {hv.x, hv.y, hv.z, hv.w};
+        f32x4 &c0 = acc[0][c & 1], &c1 = acc[1][c & 1], &c2 = acc[2][c & 1];
+        if (c < FWD_A) mfma12_a(c0, c1, c2, wf[0] + 4 * c, wf[1] + 4 * c, wf[2] + 4 * c, hk);
+        else if (c < FWD_L) mfma12_v(c0, c1, c2, wf[0] + 4 * c, wf[1] + 4 * c, wf[2] + 4 * c, hk);
+        else {
+          const float4* wp = wl + (c - FWD_L) * 3 * NTH + tid;
+          const float4 v0 = wp[0], v1 = wp[NTH], v2 = wp[2 * NTH];
+          const float w0[4] = {v0.x, v0.y, v0.z, v0.w}, w1[4] = {v1.x, v1.y, v1.z, v1.w};
+          const float w2[4] = {v2.x, v2.y, v2.z, v2.w};
+          if (c < KC - 2) mfma12_v(c0, c1, c2, w0, w1, w2, hk);
+          else mfma12_v_last(c0, c1, c2, w0, w1, w2, hk);   // the last statement of either accumulator set
+        }
+      }
+    } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int c = 0; c < KC; ++c) {
+        const float4 hv = *reinterpret_cast<const float4*>(hrow + 16 * c);
+        const float hk[4] = {hv.x, hv.y, hv.z, hv.w};
 #pragma unroll
-        for (int g = 0; g < 3; ++g) acc[g][c & 1] = mfma4(wf[g][4 * c + j], hk[j], acc[g][c & 1]);
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int g = 0; g < 3; ++g) acc[g][c & 1] = mfma4(wf[g][4 * c + j], hk[j], acc[g][c & 1]);
+      }
     }
     f32x4 a[3];
 #pragma unroll
@@ -216,7 +334,11 @@ __global__ void __launch_bounds__(NTH, 1) gru32_bwd(const float* __restrict__ do
   constexpr int KC = KO / 16;                  // float4 chunks of k
   constexpr int DP = KO + 4;                   // floats per batch row of the dgh image (16-B stagger)
   constexpr int NGR = P * MGR / NTH;           // granules swept per lane: both elements' P partials
+  constexpr int SW = sweep_width<H>(NGR);      // of them per sweep call
+  constexpr bool WIDE = H == 1024;             // W^T's statements from BWD_L on in dynamic LDS
   __shared__ __attribute__((aligned(16))) float dimg[2 * BG * DP];   // own dgh of step s in image s & 1
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float4* const wl = reinterpret_cast<float4*>(smem);
 
   int d, bgl, m;
   if (!place(P, ndir * nbg, d, bgl, m, nbg)) return;
@@ -226,20 +348,46 @@ __global__ void __launch_bounds__(NTH, 1) gru32_bwd(const float* __restrict__ do
   const int gg = d * nbg_all + bg;
   unsigned long long* xg = xch + (int64_t)gg * 2 * P * P * MGR;
   bool dead = false;
-  const bool local = same_xcd(ids + gg * IDS_PER_GROUP, P, m, fail, dead);
+  const bool local = same_xcd(ids + gg * ids_stride<H>(), P, m, fail, dead);
 
   // A = W_hh^T: row = output unit w*H/4 + 16t + lr, k = 16c + 4lq + j (gate k >> 5, own unit k & 31) in
   // wt[t][4c + j]
   float wt[NT][4 * KC];
+  if constexpr (WIDE) {   // statement (k-step 4c + j, tiles 8hf .. 8hf + 7) by statement: into AGPRs, VGPRs or LDS
+    static_assert(H != 1024 || NT == 16, "two statements of 8 tiles per k-step");
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+    for (int kk = 0; kk < 4 * KC; ++kk)
 #pragma unroll
-    for (int c = 0; c < KC; ++c)
+      for (int hf = 0; hf < 2; ++hf) {
+        const int st = 2 * kk + hf;
+        const int k = 16 * (kk >> 2) + 4 * lq + (kk & 3);
+        const float* wp = W + (int64_t)((k >> 5) * H + m * UPM + (k & 31)) * H + w * (H / 4) + lr;
+        float v[8];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int k = 16 * c + 4 * lq + j;
-        wt[t][4 * c + j] = W[(int64_t)((k >> 5) * H + m * UPM + (k & 31)) * H + w * (H / 4) + 16 * t + lr];
+        for (int i = 0; i < 8; ++i) v[i] = wp[16 * (8 * hf + i)];
+        if (st >= BWD_L) {
+          wl[((st - BWD_L) * 2) * NTH + tid] = make_float4(v[0], v[1], v[2], v[3]);
+          wl[((st - BWD_L) * 2 + 1) * NTH + tid] = make_float4(v[4], v[5], v[6], v[7]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            wt[8 * hf + i][kk] = v[i];
+            pin_f32(wt[8 * hf + i][kk], st < BWD_A);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
+  } else {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int c = 0; c < KC; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = 16 * c + 4 * lq + j;
+          wt[t][4 * c + j] = W[(int64_t)((k >> 5) * H + m * UPM + (k & 31)) * H + w * (H / 4) + 16 * t + lr];
+        }
+  }
 
   int be[2], ue[2], je[2];
   bool ok[2];
@@ -256,7 +404,7 @@ __global__ void __launch_bounds__(NTH, 1) gru32_bwd(const float* __restrict__ do
   // partial sums of own units from every member: tag, slot parity -> rec[e], added in member order
   auto gather = [&](int par, unsigned tag, float (&rec)[2]) __attribute__((always_inline)) {
     float r0 = 0.f, r1 = 0.f;   // granule q = 256k + tid: member k >> 1, element k & 1 (adding 0.f is exact)
-    sweep<NGR>(xg + ((int64_t)par * P + m) * P * MGR, [tag](unsigned long long x) { return (unsigned)(x >> 32) == tag; },
+    sweep_parts<NGR, SW>(xg + ((int64_t)par * P + m) * P * MGR, [tag](unsigned long long x) { return (unsigned)(x >> 32) == tag; },
                [&](int q, unsigned long long x) {
                  const float v = __uint_as_float((unsigned)x);
                  const bool hi = (q >> 8) & 1;
@@ -315,23 +463,69 @@ __global__ void __launch_bounds__(NTH, 1) gru32_bwd(const float* __restrict__ do
 #pragma unroll
       for (int tt = 0; tt < NT; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
       const float* grow = img + lr * DP + 4 * lq;
+      if constexpr (WIDE) {
+        float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0;
 #pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        const float4 gv = *reinterpret_cast<const float4*>(grow + 16 * c);
-        const float gk[4] = {gv.x, gv.y, gv.z, gv.w};
+        for (int c = 0; c < KC; ++c) {
+          const float4 gv = *reinterpret_cast<const float4*>(grow + 16 * c);
+          const float gk[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
+          for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
-          for (int tt = 0; tt < NT; ++tt) acc[tt] = mfma4(wt[tt][4 * c + jj], gk[jj], acc[tt]);
+            for (int hf = 0; hf < 2; ++hf) {
+              const int kk = 4 * c + jj, st = 2 * kk + hf;
+              f32x4* a = acc + 8 * hf;
+              float (*x)[4 * KC] = wt + 8 * hf;
+              // an LDS statement's values are read one statement ahead, and no further (the fence below): read
+              // all at once they would be 80 live registers
+              const float4 v0 = n0, v1 = n1;
+              if (st + 1 >= BWD_L && st + 1 < 8 * KC) {
+                n0 = wl[(st + 1 - BWD_L) * 2 * NTH + tid];
+                n1 = wl[((st + 1 - BWD_L) * 2 + 1) * NTH + tid];
+              }
+              if (st < BWD_A)
+                mfma8_a(a, x[0][kk], x[1][kk], x[2][kk], x[3][kk], x[4][kk], x[5][kk], x[6][kk], x[7][kk], gk[jj]);
+              else if (st < BWD_L)
+                mfma8_v(a, x[0][kk], x[1][kk], x[2][kk], x[3][kk], x[4][kk], x[5][kk], x[6][kk], x[7][kk], gk[jj]);
+              else if (st < 8 * KC - 2)
+                mfma8_v(a, v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, gk[jj]);
+              else   // either half's last statement
+                mfma8_v_last(a, v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, gk[jj]);
+              if (st + 1 >= BWD_L) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+          const float4 gv = *reinterpret_cast<const float4*>(grow + 16 * c);
+          const float gk[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+            for (int tt = 0; tt < NT; ++tt) acc[tt] = mfma4(wt[tt][4 * c + jj], gk[jj], acc[tt]);
+        }
       }
       unsigned long long* slot = xg + (int64_t)(s & 1) * P * P * MGR;
       const unsigned tag = (unsigned)(s + 1);
+      if constexpr (WIDE) {
+        // tile 0's address made opaque once per step, the others a constant away from it (the same addresses
+        // as below): built from the loop's invariants, all 16 tiles' 64-bit addresses stay live across the step
+        unsigned long long* base = slot + ((int64_t)(w * (H / 128)) * P + m) * MGR + lq * 16 + lr;
+        asm volatile("" : "+v"(base));
 #pragma unroll
-      for (int tt = 0; tt < NT; ++tt) {
-        const int ju = w * (H / 4) + 16 * tt + 4 * lq;   // first of this lane's 4 output units (one member's)
-        unsigned long long* dst = slot + ((int64_t)(ju >> 5) * P + m) * MGR + ((tt & 1) * 16 + lq) * 16 + lr;
+        for (int tt = 0; tt < NT; ++tt) {
+          unsigned long long* dst = base + (int64_t)(tt >> 1) * P * MGR + (tt & 1) * 256;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) put_granule(dst + i * 64, tag, __float_as_uint(acc[tt][i]), local);
+          for (int i = 0; i < 4; ++i) put_granule(dst + i * 64, tag, __float_as_uint(acc[tt][i]), local);
+        }
+      } else {
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) {
+          const int ju = w * (H / 4) + 16 * tt + 4 * lq;   // first of this lane's 4 output units (one member's)
+          unsigned long long* dst = slot + ((int64_t)(ju >> 5) * P + m) * MGR + ((tt & 1) * 16 + lq) * 16 + lr;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) put_granule(dst + i * 64, tag, __float_as_uint(acc[tt][i]), local);
+        }
       }
     }
   }
@@ -344,15 +538,17 @@ __global__ void __launch_bounds__(NTH, 1) gru32_bwd(const float* __restrict__ do
   }
 }
 
-bool supported32(int64_t H) { return H == 256 || H == 512; }
+bool supported32(int64_t H) { return H == 256 || H == 512 || H == 1024; }
 int64_t ngroups_all(int64_t B, int ndir) { return (int64_t)ndir * ((B + BG - 1) / BG); }
-// workspace: [fail word block 16 B][ids: groups x 16 x 8 B][exchange slots]
-int64_t hdr_bytes(int64_t B, int ndir) { return 16 + ngroups_all(B, ndir) * IDS_PER_GROUP * 8; }
+// workspace: [fail word block 16 B][ids: groups x 16 (H = 1024: 32) x 8 B][exchange slots]
+int64_t hdr_bytes(int64_t B, int64_t H, int ndir) {
+  return 16 + ngroups_all(B, ndir) * (H == 1024 ? ids_stride<1024>() : ids_stride<512>()) * 8;
+}
 int64_t fwd_bytes(int64_t B, int64_t H, int ndir) {
-  return hdr_bytes(B, ndir) + ngroups_all(B, ndir) * 2 * (H / UPM) * MGR * 8;
+  return hdr_bytes(B, H, ndir) + ngroups_all(B, ndir) * 2 * (H / UPM) * MGR * 8;
 }
 int64_t bwd_bytes(int64_t B, int64_t H, int ndir) {
-  return hdr_bytes(B, ndir) + ngroups_all(B, ndir) * 2 * (H / UPM) * (H / UPM) * MGR * 8;
+  return hdr_bytes(B, H, ndir) + ngroups_all(B, ndir) * 2 * (H / UPM) * (H / UPM) * MGR * 8;
 }
 
 // batch groups per launch: every direction of a batch group in the same launch, at most LAUNCH_BUDGET
@@ -364,13 +560,22 @@ int groups_per_launch(int64_t H, int ndir) {
 }
 
 template <typename K, typename... A>
-int launch_chunks(K kernel, int64_t B, int64_t H, int ndir, hipStream_t st, A... args) {
+int launch_chunks(K kernel, size_t lds, int64_t B, int64_t H, int ndir, hipStream_t st, A... args) {
   const int P = (int)(H / UPM);
   const int nbg_all = (int)((B + BG - 1) / BG), step = groups_per_launch(H, ndir);
   for (int bg0 = 0; bg0 < nbg_all; bg0 += step) {
     const int nbg = nbg_all - bg0 < step ? nbg_all - bg0 : step;
-    hipLaunchKernelGGL(kernel, dim3(grid_blocks(P, ndir * nbg)), dim3(NTH), 0, st, args..., nbg_all, bg0, nbg);
+    hipLaunchKernelGGL(kernel, dim3(grid_blocks(P, ndir * nbg)), dim3(NTH), lds, st, args..., nbg_all, bg0, nbg);
     B2P_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// the H = 1024 kernels' dynamic LDS is above the 64 KB a launch gets unasked (once per kernel, as grumc's launch_mc)
+int wide_lds(bool& done, const void* kernel, size_t lds) {
+  if (!done) {
+    B2P_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    done = true;
   }
   return 0;
 }
@@ -387,9 +592,9 @@ extern "C" int64_t b2p_gru32_workspace(int64_t B, int64_t H, int ndir) {
 // launches (a node of a captured graph) and the workspace carved. 0 go on, 1 / 2 error set, -1 nothing to do.
 static int prepare32(const char* who, bool pointers, void* ws, int64_t zero_bytes, int64_t B, int64_t T, int64_t H,
                      int ndir, hipStream_t st, XchWs* w) {
-  if (int r = xch_check_args(who, pointers, supported32(H), H, "256 or 512", ndir, ws, B, T)) return r;
+  if (int r = xch_check_args(who, pointers, supported32(H), H, "256, 512 or 1024", ndir, ws, B, T)) return r;
   B2P_CHECK_ARG(B < (1ll << 24) && T < (1ll << 30), "%s: B or T out of range", who);
-  return xch_prepare(ws, hdr_bytes(B, ndir), zero_bytes, st, w);
+  return xch_prepare(ws, hdr_bytes(B, H, ndir), zero_bytes, st, w);
 }
 
 extern "C" int b2p_gru_fwd32(const float* gi, const float* whh, const float* bhh, const float* h0, float* out,
@@ -399,8 +604,14 @@ extern "C" int b2p_gru_fwd32(const float* gi, const float* whh, const float* bhh
   XchWs w;
   if (int r = prepare32("gru32 fwd", gi && whh && out && saved, workspace, fwd_bytes(B, H, ndir), B, T, H, ndir, st, &w))
     return r < 0 ? 0 : r;
-  return launch_chunks(H == 256 ? gru32_fwd<256> : gru32_fwd<512>, B, H, ndir, st, gi, whh, bhh, h0, out, saved, w.xch,
-                       w.ids, w.fail, (int)B, (int)T, ndir);
+  if (H == 1024) {
+    static bool attr = false;
+    if (int r = wide_lds(attr, (const void*)gru32_fwd<1024>, fwd_lds<1024>())) return r;
+    return launch_chunks(gru32_fwd<1024>, fwd_lds<1024>(), B, H, ndir, st, gi, whh, bhh, h0, out, saved, w.xch, w.ids,
+                         w.fail, (int)B, (int)T, ndir);
+  }
+  return launch_chunks(H == 256 ? gru32_fwd<256> : gru32_fwd<512>, 0, B, H, ndir, st, gi, whh, bhh, h0, out, saved,
+                       w.xch, w.ids, w.fail, (int)B, (int)T, ndir);
 }
 
 extern "C" int b2p_gru_bwd32(const float* dout, const float* whh, const float* out, const float* saved,
@@ -411,6 +622,12 @@ extern "C" int b2p_gru_bwd32(const float* dout, const float* whh, const float* o
   if (int r = prepare32("gru32 bwd", dout && whh && out && saved && dgi && dgh, workspace, bwd_bytes(B, H, ndir), B, T,
                         H, ndir, st, &w))
     return r < 0 ? 0 : r;
-  return launch_chunks(H == 256 ? gru32_bwd<256> : gru32_bwd<512>, B, H, ndir, st, dout, whh, out, saved, h0, dgi, dgh,
-                       dh0, w.xch, w.ids, w.fail, (int)B, (int)T, ndir);
+  if (H == 1024) {
+    static bool attr = false;
+    if (int r = wide_lds(attr, (const void*)gru32_bwd<1024>, bwd_lds<1024>())) return r;
+    return launch_chunks(gru32_bwd<1024>, bwd_lds<1024>(), B, H, ndir, st, dout, whh, out, saved, h0, dgi, dgh, dh0,
+                         w.xch, w.ids, w.fail, (int)B, (int)T, ndir);
+  }
+  return launch_chunks(H == 256 ? gru32_bwd<256> : gru32_bwd<512>, 0, B, H, ndir, st, dout, whh, out, saved, h0, dgi,
+                       dgh, dh0, w.xch, w.ids, w.fail, (int)B, (int)T, ndir);
 }

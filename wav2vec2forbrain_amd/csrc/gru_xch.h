@@ -9,7 +9,7 @@
 namespace {
 constexpr int XCH_NTH = 256;        // threads of a member workgroup (the sweep's lane stride)
 constexpr unsigned SPIN_MAX = 1u << 22;
-constexpr int IDS_PER_GROUP = 16;   // members' XCC ids (P <= 16)
+constexpr int IDS_PER_GROUP = 16;   // members' XCC ids (P <= 16; gru32.hip at H = 1024, P = 32, strides 32 of its own)
 
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 
@@ -63,6 +63,22 @@ __device__ __forceinline__ void sweep(const unsigned long long* slot, Tag tag_ok
   }
 #pragma unroll
   for (int k = 0; k < N; ++k) dst(k * XCH_NTH + lane, v[k]);
+}
+
+// the sweep over a slot's NGR granules per lane, SW of them per call (one call when SW == NGR): the sweep keeps
+// every granule it polls in registers, which the H = 1024 kernels cannot spare for all NGR at once. dst still
+// sees the granules in ascending q.
+template <int NGR, int SW, typename Tag, typename Dst>
+__device__ __forceinline__ void sweep_parts(const unsigned long long* slot, Tag tag_ok, Dst dst, int* fail, bool& dead) {
+  static_assert(NGR % SW == 0, "whole parts");
+  if constexpr (SW == NGR) {
+    sweep<NGR>(slot, tag_ok, dst, fail, dead);
+  } else {
+#pragma unroll
+    for (int c = 0; c < NGR / SW; ++c)
+      sweep<SW>(slot + c * SW * XCH_NTH, tag_ok, [&](int q, unsigned long long x) { dst(q + c * SW * XCH_NTH, x); }, fail,
+                dead);
+  }
 }
 
 // recurrence (d, bg) and member of this block; false for blocks with no work

@@ -46,19 +46,7 @@ template <int H>
 constexpr int sweep_width(int ngr) { return H == 1024 ? SW1024 : ngr; }
 template <int H>
 constexpr int bwd_images() { return H == 1024 ? 1 : 2; }
-// the shared sweep over a slot's NGR granules per lane, SW of them per call (one call when SW == NGR)
-template <int NGR, int SW, typename Tag, typename Dst>
-__device__ __forceinline__ void sweep_parts(const unsigned long long* slot, Tag tag_ok, Dst dst, int* fail, bool& dead) {
-  static_assert(NGR % SW == 0, "whole parts");
-  if constexpr (SW == NGR) {
-    sweep<NGR>(slot, tag_ok, dst, fail, dead);
-  } else {
-#pragma unroll
-    for (int c = 0; c < NGR / SW; ++c)
-      sweep<SW>(slot + c * SW * XCH_NTH, tag_ok, [&](int q, unsigned long long x) { dst(q + c * SW * XCH_NTH, x); }, fail,
-                dead);
-  }
-}
+// (sweep_parts, csrc/gru_xch.h: SW granules per sweep call)
 
 __device__ __forceinline__ unsigned pack2(float a, float b) {
   return (unsigned)b2p_bf16_bits(a) | ((unsigned)b2p_bf16_bits(b) << 16);

@@ -980,8 +980,11 @@ def _x3_single(A, B) -> bool:
 # reference's trajectory (tools/ft_policy_ab.py, profiles/r06m_ft_policy_ab.txt): three-term everywhere
 # 8.1e-5 at step 3, 91.6 ms/step; this set 2.1e-4, 83.6 ms; forward single-pass (fp16) or two-term
 # 3.1e-3 .. 1.4e-2, backward-data single-pass 2.2e-3 (both past the 1e-3 gate).
-# B2P_X3_POLICY=<roles> overrides it ('none': three-term everywhere).
-X3_POLICY_FORMS = frozenset(filter(None, os.environ.get("B2P_X3_POLICY", "wgrad,dgrad2b").replace("none", "").split(",")))
+# 'gru32w' is no GEMM role (x3_mfma_work ignores it): it lets a GRU layer wider than 512 (H = 1024) take the
+# persistent exact-fp32 recurrence, the only one with a backward at that size off the 16-bit path
+# (_gru_recurrence), so that a full fine-tune of a 1024-wide encoder trains with nothing set.
+# B2P_X3_POLICY=<roles> overrides it ('none': three-term everywhere, nothing selected).
+X3_POLICY_FORMS = frozenset(filter(None, os.environ.get("B2P_X3_POLICY", "wgrad,dgrad2b,gru32w").replace("none", "").split(",")))
 
 
 def x3_mfma_work(forms) -> float:
@@ -1551,6 +1554,8 @@ _GRU32 = [True]
 # bit for bit: its recorded trajectories have a 1e-4 gate that another (equally accurate) summation
 # order can move past (the ATTN32_MODES decision); GRU32_MODES = (1, 3) is the request.
 GRU32_MODES = (3,)
+# the largest hidden size that takes "gru32" with no form asked for; above it: the 'gru32w' form
+_GRU32_NARROW_MAX = 512
 
 
 @contextlib.contextmanager
@@ -1578,7 +1583,10 @@ def _gru_recurrence(H: int) -> str:
     if fast and _GRUMC[0] and lib.b2p_gru_mc_supported(H):
         return "mc"
     if not fast and _state.prec in GRU32_MODES and _GRU32[0] and lib.b2p_gru32_supported(H):
-        return "gru32"
+        # a size only the wide class covers (H = 1024: P = 32 members) is opted into by the 'gru32w' form, as
+        # the 16-bit path is by 'grurec1'; without it the size stays on "step" (a forward and no backward)
+        if H <= _GRU32_NARROW_MAX or "gru32w" in (_state.x3forms or ()):
+            return "gru32"
     return "step"
 
 

@@ -252,7 +252,8 @@ class Trainer:
 
     def precision_context(self):
         """The precision mode of this Trainer's steps (step_precision) and, in the bf16x3 policy, its
-        per-role GEMM forms (functional.X3_POLICY_FORMS)."""
+        forms (functional.X3_POLICY_FORMS: the per-role GEMM forms, and 'gru32w', with which a GRU encoder of
+        hidden size 1024 takes the persistent exact-fp32 recurrence and so has a backward)."""
         mode = self.step_precision()
         stack = contextlib.ExitStack()
         if mode is not None:
