@@ -71,7 +71,29 @@ typedef struct {
   int64_t conv_sample_stride;
 } b2p_operand;
 
-enum { B2P_ACT_NONE = 0, B2P_ACT_GELU = 1, B2P_ACT_SOFTSIGN = 2, B2P_ACT_SILU = 3 };
+/* Activation ids. 0-3 are fused by the GEMM epilogues (b2p_epilogue.act / act_bwd,
+ * b2p_act_dropout_cast16) and accepted everywhere. The ids after them (transformers' ACT2FN
+ * definitions) are served by the elementwise b2p_act_fwd / b2p_act_bwd only; every other entry
+ * point rejects them. An id outside the table is an error, never identity. */
+enum {
+  B2P_ACT_NONE = 0,
+  B2P_ACT_GELU = 1,       /* x Phi(x), erf form                                                    */
+  B2P_ACT_SOFTSIGN = 2,
+  B2P_ACT_SILU = 3,
+  B2P_ACT_GELU_TANH = 4,  /* 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))): gelu_new, gelu_fast,
+                           * gelu_pytorch_tanh, gelu_accurate                                      */
+  B2P_ACT_GELU_10 = 5,    /* clip(gelu(x), -10, 10); derivative 0 where the clip is active         */
+  B2P_ACT_QUICK_GELU = 6, /* x sigmoid(1.702 x)                                                    */
+  B2P_ACT_LAPLACE = 7,    /* 0.5 (1 + erf((x - 0.707107) / (0.282095 sqrt 2)))                     */
+  B2P_ACT_MISH = 8,       /* x tanh(softplus(x))                                                   */
+  B2P_ACT_RELU = 9,       /* max(x, 0); derivative 0 at 0                                          */
+  B2P_ACT_RELU2 = 10,     /* max(x, 0)^2                                                           */
+  B2P_ACT_RELU6 = 11,     /* min(max(x, 0), 6); derivative 1 on (0, 6), else 0                     */
+  B2P_ACT_SIGMOID = 12,
+  B2P_ACT_TANH = 13,
+  B2P_ACT_EPILOGUE_LAST = B2P_ACT_SILU,
+  B2P_ACT_LAST = B2P_ACT_TANH
+};
 enum { B2P_EPI_C16_FP16 = 1 };
 
 typedef struct {
@@ -282,7 +304,14 @@ int b2p_softmax_fwd(const float* S, float* P, float* Pd, int64_t rows, int64_t n
 int b2p_softmax_bwd(const float* P, const float* dPd, float* dS, int64_t rows, int64_t n,
                     int64_t ld, float drop_p, uint64_t drop_seed, b2p_stream_t stream);
 
-/* elementwise activation backward: dx = dy * act'(pre) (optionally after dropout of dy) */
+/* elementwise activation forward over the whole table (0..B2P_ACT_LAST): out = act(pre), out == pre
+ * allowed. 16-byte accesses when n % 4 == 0 and both pointers are 16-byte aligned, scalar ones
+ * otherwise. An id outside the table is an error. This is how an activation the GEMM epilogue does
+ * not fuse (id > B2P_ACT_EPILOGUE_LAST) is applied: GEMM with bias and C = the pre-activation, then
+ * this launch. */
+int b2p_act_fwd(const float* pre, float* out, int64_t n, int act, b2p_stream_t stream);
+/* elementwise activation backward over the whole table: dx = dy * act'(pre). An id outside the table
+ * is an error. */
 int b2p_act_bwd(const float* dy, const float* pre, float* dx, int64_t n, int act,
                 b2p_stream_t stream);
 

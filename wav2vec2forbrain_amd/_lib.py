@@ -100,6 +100,7 @@ _SIGS = {
     "b2p_cast_bf16": (c_i32, [c_p, c_p, c_i64, c_p]),
     "b2p_softmax_fwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_u64, c_p]),
     "b2p_softmax_bwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_u64, c_p]),
+    "b2p_act_fwd": (c_i32, [c_p, c_p, c_i64, c_i32, c_p]),
     "b2p_act_bwd": (c_i32, [c_p, c_p, c_p, c_i64, c_i32, c_p]),
     "b2p_gauss_smooth": (c_i32, [c_p, c_p, c_i32, c_p, c_i64, c_i64, c_i64, c_p]),
     "b2p_unfold_col2im": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_p]),

@@ -898,6 +898,10 @@ extern "C" int b2p_rotary16(const float* x, const float* cos_t, const float* sin
 extern "C" int b2p_act_dropout_cast16(const float* pre, uint16_t* out, int64_t n, int act, float p, uint64_t seed,
                                       b2p_stream_t stream) {
   B2P_CHECK_ARG(pre && out, "act_dropout_cast16: NULL pointer");
+  B2P_CHECK_ARG(act >= 0 && act <= B2P_ACT_EPILOGUE_LAST,
+                "act_dropout_cast16: activation id %d is not one of 0..%d (the ids a GEMM epilogue fuses); "
+                "b2p_act_fwd serves the others",
+                act, B2P_ACT_EPILOGUE_LAST);
   B2P_CHECK_ARG(p >= 0.f && p < 1.f, "act_dropout_cast16: p in [0,1)");
   B2P_CHECK_ARG(n % 4 == 0 && ((uintptr_t)pre & 15u) == 0 && ((uintptr_t)out & 7u) == 0,
                 "act_dropout_cast16: n % 4 == 0 and aligned pointers required");

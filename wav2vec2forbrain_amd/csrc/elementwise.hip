@@ -2,10 +2,12 @@
 // activation backward, front-end smoothing / col2im, weight layout transforms, weight norm.
 // All fp32, float4-vectorised along the contiguous dimension where the layout allows.
 #include "common.h"
+#include "act.h"
 #include <stdlib.h>
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include "../../include/b2p_hip.h"
@@ -883,28 +885,39 @@ __global__ void __launch_bounds__(256) softmax_bwd_k(const float* __restrict__ P
   }
 }
 
-__device__ __forceinline__ float act_bwd_one(float dy, float x, int act) {
-  float g = 1.f;
-  if (act == B2P_ACT_GELU) g = b2p_gelu_grad(x);
-  else if (act == B2P_ACT_SOFTSIGN) { const float d = 1.f + fabsf(x); g = 1.f / (d * d); }
-  else if (act == B2P_ACT_SILU) g = b2p_silu_grad(x);
-  return dy * g;
-}
+// dx = dy * act'(pre), the activation a template parameter (act.h): no id chain in the element loop
+template <int ACT>
 __global__ void act_bwd_k(const float* __restrict__ dy, const float* __restrict__ pre, float* __restrict__ dx,
-                          int64_t n, int act) {
+                          int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  dx[i] = act_bwd_one(dy[i], pre[i], act);
+  dx[i] = dy[i] * b2p_act_grad<ACT>(pre[i]);
 }
 // 4 elements per thread through 16-byte accesses (the front end's softsign' over B x L x 256: the scalar
 // form ran at ~1 TB/s), same expression per element
+template <int ACT>
 __global__ void act_bwd4_k(const float4* __restrict__ dy, const float4* __restrict__ pre, float4* __restrict__ dx,
-                           int64_t n4, int act) {
+                           int64_t n4) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n4) return;
   const float4 d = dy[i], x = pre[i];
-  dx[i] = make_float4(act_bwd_one(d.x, x.x, act), act_bwd_one(d.y, x.y, act), act_bwd_one(d.z, x.z, act),
-                      act_bwd_one(d.w, x.w, act));
+  dx[i] = make_float4(d.x * b2p_act_grad<ACT>(x.x), d.y * b2p_act_grad<ACT>(x.y), d.z * b2p_act_grad<ACT>(x.z),
+                      d.w * b2p_act_grad<ACT>(x.w));
+}
+// out = act(pre), out == pre allowed (each thread reads its elements before it writes them): no
+// __restrict__ on the pair
+template <int ACT>
+__global__ void act_fwd_k(const float* pre, float* out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = b2p_act_val<ACT>(pre[i]);
+}
+template <int ACT>
+__global__ void act_fwd4_k(const float4* pre, float4* out, int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float4 x = pre[i];
+  out[i] = make_float4(b2p_act_val<ACT>(x.x), b2p_act_val<ACT>(x.y), b2p_act_val<ACT>(x.z), b2p_act_val<ACT>(x.w));
 }
 
 // ------------------------------------------------------------------ front-end
@@ -1706,15 +1719,52 @@ extern "C" int b2p_softmax_bwd(const float* P, const float* dPd, float* dS, int6
   return 0;
 }
 
+// one host switch per launch over the activation table: F is a generic lambda taking the id as an
+// integral constant. The callers have checked the id.
+template <class F> static void act_dispatch(int act, F&& f) {
+  switch (act) {
+#define B2P_ACT_CASE(A) case A: f(std::integral_constant<int, A>{}); return;
+    B2P_ACT_CASE(B2P_ACT_NONE) B2P_ACT_CASE(B2P_ACT_GELU) B2P_ACT_CASE(B2P_ACT_SOFTSIGN) B2P_ACT_CASE(B2P_ACT_SILU)
+    B2P_ACT_CASE(B2P_ACT_GELU_TANH) B2P_ACT_CASE(B2P_ACT_GELU_10) B2P_ACT_CASE(B2P_ACT_QUICK_GELU)
+    B2P_ACT_CASE(B2P_ACT_LAPLACE) B2P_ACT_CASE(B2P_ACT_MISH) B2P_ACT_CASE(B2P_ACT_RELU) B2P_ACT_CASE(B2P_ACT_RELU2)
+    B2P_ACT_CASE(B2P_ACT_RELU6) B2P_ACT_CASE(B2P_ACT_SIGMOID) B2P_ACT_CASE(B2P_ACT_TANH)
+#undef B2P_ACT_CASE
+  }
+}
+
+extern "C" int b2p_act_fwd(const float* pre, float* out, int64_t n, int act, b2p_stream_t stream) {
+  B2P_CHECK_ARG(act >= 0 && act <= B2P_ACT_LAST, "act_fwd: activation id %d is outside the table (0..%d)", act,
+                B2P_ACT_LAST);
+  B2P_CHECK_ARG(pre && out, "act_fwd: NULL pointer");
+  if (n <= 0) return 0;
+  const bool v4 = n % 4 == 0 && (((uintptr_t)pre | (uintptr_t)out) & 15u) == 0;
+  act_dispatch(act, [&](auto A) {
+    if (v4)
+      hipLaunchKernelGGL(act_fwd4_k<decltype(A)::value>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)stream,
+                         reinterpret_cast<const float4*>(pre), reinterpret_cast<float4*>(out), n / 4);
+    else
+      hipLaunchKernelGGL(act_fwd_k<decltype(A)::value>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, pre,
+                         out, n);
+  });
+  B2P_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int b2p_act_bwd(const float* dy, const float* pre, float* dx, int64_t n, int act, b2p_stream_t stream) {
+  B2P_CHECK_ARG(act >= 0 && act <= B2P_ACT_LAST, "act_bwd: activation id %d is outside the table (0..%d)", act,
+                B2P_ACT_LAST);
   B2P_CHECK_ARG(dy && pre && dx, "act_bwd: NULL pointer");
   if (n <= 0) return 0;
-  if (n % 4 == 0 && (((uintptr_t)dy | (uintptr_t)pre | (uintptr_t)dx) & 15u) == 0)
-    hipLaunchKernelGGL(act_bwd4_k, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(pre),
-                       reinterpret_cast<float4*>(dx), n / 4, act);
-  else
-    hipLaunchKernelGGL(act_bwd_k, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, dy, pre, dx, n, act);
+  const bool v4 = n % 4 == 0 && (((uintptr_t)dy | (uintptr_t)pre | (uintptr_t)dx) & 15u) == 0;
+  act_dispatch(act, [&](auto A) {
+    if (v4)
+      hipLaunchKernelGGL(act_bwd4_k<decltype(A)::value>, dim3(nblocks(n / 4)), dim3(256), 0, (hipStream_t)stream,
+                         reinterpret_cast<const float4*>(dy), reinterpret_cast<const float4*>(pre),
+                         reinterpret_cast<float4*>(dx), n / 4);
+    else
+      hipLaunchKernelGGL(act_bwd_k<decltype(A)::value>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, dy, pre,
+                         dx, n);
+  });
   B2P_CHECK_LAUNCH();
   return 0;
 }

@@ -473,6 +473,12 @@ extern "C" int b2p_gemm(const b2p_gemm_desc* dp, b2p_stream_t stream) {
   B2P_CHECK_ARG(d.nz1 >= 1 && d.nz2 >= 1, "gemm: batch dims must be >= 1");
   B2P_CHECK_ARG(d.precision >= 0 && d.precision <= 3,
                 "gemm: precision must be 0 (bf16), 1 (fp32), 2 (fp16) or 3 (split bf16)");
+  // the epilogues know ids 0..3 and would treat any other as identity
+  B2P_CHECK_ARG(d.ep.act >= 0 && d.ep.act <= B2P_ACT_EPILOGUE_LAST && d.ep.act_bwd >= 0 &&
+                    d.ep.act_bwd <= B2P_ACT_EPILOGUE_LAST,
+                "gemm: the epilogue fuses activation ids 0..%d only (act=%d, act_bwd=%d): store the pre-activation "
+                "and apply b2p_act_fwd / b2p_act_bwd",
+                B2P_ACT_EPILOGUE_LAST, d.ep.act, d.ep.act_bwd);
   if (d.M == 0 || d.N == 0) return 0;
   B2P_CHECK_ARG(d.ep.C != nullptr || d.ep.C16 != nullptr, "gemm: C and C16 are NULL");
   B2P_CHECK_ARG(d.ep.C != nullptr || d.ep.beta == 0.f, "gemm: beta != 0 needs C");

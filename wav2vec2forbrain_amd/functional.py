@@ -30,7 +30,20 @@ import torch
 from . import _lib
 from ._lib import GemmDesc, Operand, Epilogue
 
-ACT = {"none": 0, None: 0, "gelu": 1, "softsign": 2, "silu": 3, "swish": 3}
+# activation name -> B2P_ACT_* id (include/b2p_hip.h). The names after "swish" are transformers'
+# ACT2FN keys (the reference's ACTIVATION_FUNCTION literal); the four tanh-GELU spellings are one id
+ACT = {"none": 0, None: 0, "gelu": 1, "softsign": 2, "silu": 3, "swish": 3,
+       "linear": 0, "gelu_python": 1,
+       "gelu_new": 4, "gelu_fast": 4, "gelu_pytorch_tanh": 4, "gelu_accurate": 4,
+       "gelu_10": 5, "quick_gelu": 6, "laplace": 7, "mish": 8, "relu": 9, "relu2": 10, "relu6": 11,
+       "sigmoid": 12, "tanh": 13}
+# the ids a GEMM epilogue fuses (act / act_bwd of gemm()); the others run as b2p_act_fwd / b2p_act_bwd
+# launches of their own (_Linear)
+EPILOGUE_ACTS = frozenset({0, 1, 2, 3})
+_ACT_NAME = {}
+for _k, _v in ACT.items():
+    if _k is not None:
+        _ACT_NAME.setdefault(_v, _k)
 
 class _State:
     # process-global (autograd runs backward on its own worker thread, so a thread-local
@@ -836,6 +849,10 @@ def gemm(M, N, K, A: Operand, B: Operand, C, ldc, c_off=0, cbs1=0, cbs2=0, nz1=1
          aux16=None, colsum_part=None, c16_fp16=False, C16b=None):
     """C may be None when only the bf16 copy C16 (same strides) is wanted. Both operands bf16
     (Operand.dtype 1) selects the LDS-DMA kernel (gemm16.hip)."""
+    if act not in EPILOGUE_ACTS or act_bwd not in EPILOGUE_ACTS:   # (no new local: the bf16x3 branch re-calls with locals())
+        raise ValueError(f"gemm: activation {_ACT_NAME.get(act if act not in EPILOGUE_ACTS else act_bwd)!r} "
+                         f"(act={act}, act_bwd={act_bwd}) has no fused epilogue; store the pre-activation and "
+                         f"apply act_fwd / _act_bwd (as Fn.linear does)")
     if _state.prec == 3 and A.dtype == 0 and B.dtype == 0 and _x3_single(A, B):
         # bf16x3 policy with a single-pass role (forward on fp16, see _x3_single): this GEMM as in bf16 mode
         kw = dict(locals())
@@ -1172,6 +1189,13 @@ def colsum_batched(x, batch, M, N, out, ld=None, bstride=None, mode=0, y=None):
 def _dropout_raw(x, p, seed, out=None):
     out = torch.empty_like(x) if out is None else out
     _lib.call("b2p_dropout", _p(x), _p(out), x.numel(), float(p), seed, _st())
+    return out
+
+
+def act_fwd(pre, act, out=None):
+    """out = act(pre) for any id of the table (b2p_act_fwd); out may be pre itself."""
+    out = torch.empty_like(pre) if out is None else out
+    _lib.call("b2p_act_fwd", _p(pre), _p(out), pre.numel(), act, _st())
     return out
 
 
@@ -1996,8 +2020,15 @@ class _Linear(torch.autograd.Function):
         _chk(W, "linear.W")
         N, K = W.shape
         out = torch.empty(*x.shape[:-1], N, device=x.device)
-        pre = torch.empty_like(out) if act else None
-        mm_nt(x, W, out, bias=b, act=act, pre_out=pre)
+        if act in EPILOGUE_ACTS:
+            pre = torch.empty_like(out) if act else None
+            mm_nt(x, W, out, bias=b, act=act, pre_out=pre)
+        else:
+            # a table activation the epilogue does not fuse: the GEMM writes the pre-activation, one
+            # elementwise launch applies it (linear() does it in place when no gradient is recorded)
+            pre = torch.empty_like(out)
+            mm_nt(x, W, pre, bias=b)
+            act_fwd(pre, act, out)
         ctx.save_for_backward(x, W, pre)
         ctx.act = act
         ctx.has_b = b is not None
@@ -2029,7 +2060,18 @@ class _Linear(torch.autograd.Function):
 
 def linear(x, W, b=None, act=0):
     with _fp32_if("linear"):
-        return _Linear.apply(x.contiguous(), W, b, act)
+        x = x.contiguous()
+        if act not in EPILOGUE_ACTS and not (torch.is_grad_enabled() and
+                                             any(t is not None and t.requires_grad for t in (x, W, b))):
+            # eval / no_grad with a table activation: no backward will read the pre-activation, so it
+            # is applied in place and no second buffer is kept (inside _Linear.forward grad mode is
+            # always off, so the decision is taken here)
+            _chk(x, "linear.x")
+            _chk(W, "linear.W")
+            out = torch.empty(*x.shape[:-1], W.shape[0], device=x.device)
+            mm_nt(x, W, out, bias=b)
+            return act_fwd(out, act, out)
+        return _Linear.apply(x, W, b, act)
 
 
 class _Dropout(torch.autograd.Function):

@@ -11,17 +11,24 @@ ACTIVATION_FUNCTION = Literal["gelu", "gelu_10", "gelu_fast", "gelu_new", "gelu_
                               "gelu_accurate", "laplace", "linear", "mish", "quick_gelu", "relu", "relu2", "relu6",
                               "sigmoid", "silu", "swish", "tanh"]
 
-# activations with a fused HIP epilogue (GEMM act / act_bwd)
-SUPPORTED_ACTIVATIONS = {"gelu": "gelu", "gelu_python": "gelu", "silu": "silu", "swish": "silu"}
+# every name of the literal -> its key in functional.ACT. gelu / silu are fused into the GEMM epilogue
+# (act / act_bwd); the others run as one elementwise launch after the GEMM (b2p_act_fwd) and one before
+# the backward GEMMs (b2p_act_bwd). The four tanh-GELU spellings are one formula below fp32 resolution.
+SUPPORTED_ACTIVATIONS = {
+    "gelu": "gelu", "gelu_python": "gelu", "silu": "silu", "swish": "silu", "linear": "linear",
+    "gelu_new": "gelu_new", "gelu_fast": "gelu_new", "gelu_pytorch_tanh": "gelu_new", "gelu_accurate": "gelu_new",
+    "gelu_10": "gelu_10", "quick_gelu": "quick_gelu", "laplace": "laplace", "mish": "mish", "relu": "relu",
+    "relu2": "relu2", "relu6": "relu6", "sigmoid": "sigmoid", "tanh": "tanh",
+}
 
 
 class Activation(nn.Module):
-    """Parameter-free marker for an activation between two Linear layers (fused into the GEMM)."""
+    """Parameter-free marker for an activation between two Linear layers (applied by Fn.linear)."""
 
     def __init__(self, name: str):
         super().__init__()
         if name not in SUPPORTED_ACTIVATIONS:
-            raise NotImplementedError(f"activation {name!r} has no fused HIP epilogue; supported: "
+            raise NotImplementedError(f"activation {name!r} has no HIP kernel; supported: "
                                       f"{sorted(SUPPORTED_ACTIVATIONS)}")
         self.name = SUPPORTED_ACTIVATIONS[name]
 

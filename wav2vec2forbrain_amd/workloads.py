@@ -32,6 +32,16 @@ def bench_config(kind: str = "base", bs: int = 32, L: int = 1024) -> dict:
                 gru_layers=2, fc_hidden=[])
 
 
+def tiny_act_config(fc_activation: str = "gelu") -> dict:
+    """tiny_act: a two-sample, one-layer step whose brain encoder ends in fc [40] with the named
+    activation (any name of util.nn_helper.ACTIVATION_FUNCTION): GRU 16 x 3, hidden 48, 128-bin windows.
+    The workload of the activation-table fixtures (tests/golden/tiny_act.npz)."""
+    return dict(name="tiny_act", seed=43, B=2, L=128, in_lens=[128, 128], tgt_range=(3, 9), hidden_size=48, layers=1,
+                heads=3, ffn=96, pos_k=8, pos_groups=2, gru_hidden=16, gru_layers=3, bidirectional=True,
+                fc_hidden=[40], learnable_h0=False, full_grad_max=65536, infeasible=False,
+                fc_activation=fc_activation)
+
+
 def make_batch(cfg):
     """Synthetic inputs (SURVEY 8(d2)): x ~ N(0,1) (B,L,256); day ~ U{0..23}; targets ~ U{4..31}
     padded with 0; data seed 0."""
@@ -85,7 +95,8 @@ def build_model(cfg, device="cuda", seed=None, train_dropouts=False):
     args = bfe.B2P2TBrainFeatureExtractorArgsModel(
         encoder_gru_hidden_size=cfg["gru_hidden"], encoder_num_gru_layers=cfg["gru_layers"],
         encoder_bidirectional=cfg["bidirectional"], encoder_fc_hidden_sizes=list(cfg["fc_hidden"]),
-        encoder_learnable_inital_state=cfg["learnable_h0"])
+        encoder_learnable_inital_state=cfg["learnable_h0"],
+        encoder_fc_activation_function=cfg.get("fc_activation", "gelu"))
     torch.manual_seed(0)
     brain = bfe.B2P2TModel(args, bfe.B2TBrainFeatureExtractor(args, name, 256 * args.unfolder_kernel_len))
     if cfg.get("conformer"):
