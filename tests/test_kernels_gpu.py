@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.attn16_cases import keep_mask_ref as _keep_mask_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -200,29 +202,6 @@ def test_gru_layer_bf16_persistent(H, B, T, h0, unfold, f16):
         got = torch.autograd.grad(out, [xs, *wg] + ([hg] if h0 else []), dout.cuda())
     for i, (a, b) in enumerate(zip(got, refg)):
         assert _rel(a.cpu(), b) < 3e-2, i
-
-
-def _mix32(x):
-    x = x ^ (x >> np.uint32(16))
-    x = x * np.uint32(0x7feb352d)
-    x = x ^ (x >> np.uint32(15))
-    x = x * np.uint32(0x846ca68b)
-    return x ^ (x >> np.uint32(16))
-
-
-def _keep_mask_ref(seed, p, B, nh, T):
-    """numpy restatement of the dropout keep mask (csrc/common.h b2p_keep over the attention element
-    index ((b*nh + h)*T + q)*TP + key, TP = T rounded up to even): (B, nh, T, T) bool."""
-    with np.errstate(over="ignore"):
-        k = np.uint32(seed & 0xFFFFFFFF) ^ _mix32(np.uint32(((seed >> 32) + 0x9E3779B9) & 0xFFFFFFFF))
-        TP = T + (T & 1)
-        row = np.arange(B * nh * T, dtype=np.uint64)[:, None] * np.uint64(TP)
-        idx = (row + np.arange(T, dtype=np.uint64)[None, :]).astype(np.uint32)
-        h = _mix32(_mix32((idx >> np.uint32(1)) ^ k) + k)
-        half = np.where(idx & np.uint32(1), h >> np.uint32(16), h & np.uint32(0xFFFF))
-    thr = int(float(np.float32(p)) * 4294967296.0)   # b2p_dropout_threshold of the float32 p
-    thr16 = (thr >> 16) + ((thr >> 15) & 1)
-    return (half >= thr16).reshape(B, nh, T, T)
 
 
 @pytest.mark.parametrize("B,T,nh,p", [(2, 249, 12, 0.0), (2, 249, 12, 0.1), (3, 100, 4, 0.1), (1, 17, 2, 0.0),
