@@ -147,6 +147,22 @@ typedef struct {
 
 int b2p_gemm(const b2p_gemm_desc* d, b2p_stream_t stream);
 
+/* Skinny products of a 32-wide head (csrc/skinny32.hip): a descriptor of plain fp32 operands (one
+ * matrix each, no conv view, gather or batch) at precision 0 or 2, no LayerDrop gate set, alpha 1, beta 0
+ * and no epilogue beyond a bias (forward only), in one of three forms:
+ *   B2P_SKINNY32_FWD    A, B k-contiguous, N == 32, K % 4 == 0          (nn.Linear forward)
+ *   B2P_SKINNY32_DGRAD  A k-contiguous, B n-contiguous, K == 32         (its input gradient)
+ *   B2P_SKINNY32_WGRAD  A m-contiguous, B n-contiguous, M == 32         (its weight gradient; split-K as
+ *                       the descriptor says, the slabs summed by the reduce kernel b2p_gemm launches)
+ * b2p_skinny32_form names the form (B2P_SKINNY32_NONE: the descriptor is b2p_gemm's); b2p_skinny32 runs
+ * it with results equal to b2p_gemm's bit for bit and fails on a descriptor without a form. */
+#define B2P_SKINNY32_NONE 0
+#define B2P_SKINNY32_FWD 1
+#define B2P_SKINNY32_DGRAD 2
+#define B2P_SKINNY32_WGRAD 3
+int b2p_skinny32_form(const b2p_gemm_desc* d);
+int b2p_skinny32(const b2p_gemm_desc* d, b2p_stream_t stream);
+
 /* ------------------------------------------------------------------ graph-replayed steps
  * A training step captured once as a HIP graph (train/step_graph.py) replays with host values
  * frozen. Dropout: every kernel adds (*dev_counter) * 0x9E3779B97F4A7C15 to its host-drawn seed
@@ -353,6 +369,14 @@ int b2p_unfold_weight16(const float* w0, const float* w1, int64_t G, int64_t C, 
 int b2p_pad_rows16(const float* src, uint16_t* dst, int64_t B, int64_t T, int64_t N, int64_t R, int64_t lead,
                    b2p_stream_t stream);
 int b2p_cast16_tail(const float* x, uint16_t* y, int64_t n, int64_t n_total, int fp16, b2p_stream_t stream);
+/* The bf16 mode's front end in one launch (csrc/front.hip), C == 256, ntaps <= 64, precision 0 (bf16 MFMA) or 2
+ * (fp16 MFMA): xs = b2p_gauss_smooth(x); z[b] = xs[b] @ W[day[b]] + bias[day[b]] (W (n_days, C, C), bias
+ * (n_days, C); the product as b2p_gemm computes it from fp32 operands at that precision); s = softsign(z); and,
+ * when s16 != NULL, b2p_cast16_tail(s) with s16_tail zero elements behind it (fp16 when s16_fp16, else bf16).
+ * Every output equals those three calls' bit for bit. */
+int b2p_front_fwd(const float* x, const float* taps, int ntaps, const int64_t* day, int64_t n_days, const float* W,
+                  const float* bias, float* xs, float* z, float* s, uint16_t* s16, int s16_fp16, int64_t s16_tail,
+                  int64_t B, int64_t L, int64_t C, int precision, b2p_stream_t stream);
 /* records {dst, a, b, count} (int64 each; a / b may be 0 = NULL): dst[i] = a[i] + b[i] (fp32), all
  * records in one launch: the per-step assembly of stacked / concatenated small parameter tensors
  * (nn.GRU W_hh of both directions, b_ih + b_hh folds; src/model/brain_feature_extractor.py:39-47) */
@@ -488,6 +512,10 @@ int b2p_gru16_supported(int64_t H);
 int64_t b2p_gru16_lane_floats(int64_t B, int64_t T, int64_t H, int ndir, int R);
 int b2p_gru_lane_permute(const float* src, float* dst, int64_t B, int64_t T, int64_t H, int ndir,
                          int Rl, int Rs, uint32_t rmap, int to_lane, b2p_stream_t stream);
+/* LN(Rl) -> two standard (B, T, ndir*Rs*H) tensors in one pass over src: dst by rmap and dst2 by rmap2,
+ * each as b2p_gru_lane_permute(..., to_lane = 0) writes it (the backward's dgi and dgh from dgL). */
+int b2p_gru_lane_unpack2(const float* src, float* dst, float* dst2, int64_t B, int64_t T, int64_t H, int ndir,
+                         int Rl, int Rs, uint32_t rmap, uint32_t rmap2, b2p_stream_t stream);
 int b2p_gru_fwd16(const float* giL, const float* whh, const float* bhh, const float* h0,
                   float* hL, float* savL, int64_t B, int64_t T, int64_t H, int ndir,
                   b2p_stream_t stream);

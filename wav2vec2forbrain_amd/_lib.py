@@ -75,6 +75,8 @@ _SIGS = {
     "b2p_timing_enable": (c_i32, [c_i32, c_i32]),
     "b2p_timing_read": (c_i32, [c_i32, ctypes.POINTER(c_f32), ctypes.POINTER(c_i32), ctypes.POINTER(c_f64)]),
     "b2p_gemm": (c_i32, [ctypes.POINTER(GemmDesc), c_p]),
+    "b2p_skinny32_form": (c_i32, [ctypes.POINTER(GemmDesc)]),
+    "b2p_skinny32": (c_i32, [ctypes.POINTER(GemmDesc), c_p]),
     "b2p_colsum_workspace": (c_i64, [c_i64, c_i64]),
     "b2p_colsum": (c_i32, [c_p, c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_p]),
     "b2p_colsum_batched": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_i32, c_p, c_p]),
@@ -109,6 +111,8 @@ _SIGS = {
     "b2p_unfold_weight16": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i32, c_p, c_p]),
     "b2p_pad_rows16": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p]),
     "b2p_cast16_tail": (c_i32, [c_p, c_p, c_i64, c_i64, c_i32, c_p]),
+    "b2p_front_fwd": (c_i32, [c_p, c_p, c_i32, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i64, c_i64, c_i64,
+                              c_i64, c_i32, c_p]),
     "b2p_gather_recs": (c_i32, [c_p, c_i32, c_p]),
     "b2p_conv_weight_permute": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p]),
     "b2p_conv_weight_transpose_flip": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p]),
@@ -120,6 +124,7 @@ _SIGS = {
     "b2p_gru16_supported": (c_i32, [c_i64]),
     "b2p_gru16_lane_floats": (c_i64, [c_i64, c_i64, c_i64, c_i32, c_i32]),
     "b2p_gru_lane_permute": (c_i32, [c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_u32, c_i32, c_p]),
+    "b2p_gru_lane_unpack2": (c_i32, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_u32, c_u32, c_p]),
     "b2p_gru_fwd16": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p]),
     "b2p_gru_bwd16": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i32, c_p]),
     "b2p_gru_mc_supported": (c_i32, [c_i64]),

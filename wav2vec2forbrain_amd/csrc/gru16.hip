@@ -413,9 +413,11 @@ __global__ void __launch_bounds__(H * 2) gru16_bwd(const float* __restrict__ doL
 // ------------------------------------------------------------------------------ layout permutation
 // One thread per LN float4. to_lane: LN record k <- standard record rmap[k]; else standard record
 // rmap[k] <- LN record k (k < Rl). Standard tensor (B, T, ndir*Rs*H); padded batch rows of the LN
-// tensor are written as 0 (to_lane) or skipped.
-__global__ void gru_lane_permute_k(const float* __restrict__ src, float* __restrict__ dst, int B, int T, int H,
-                                   int ndir, int Rl, int Rs, unsigned rmap, int to_lane, int64_t n4) {
+// tensor are written as 0 (to_lane) or skipped. dst2 (unpacking only; may be NULL): a second standard
+// tensor that takes LN record k as its record rmap2[k] from the same read.
+__global__ void gru_lane_permute_k(const float* __restrict__ src, float* __restrict__ dst, float* __restrict__ dst2,
+                                   int B, int T, int H, int ndir, int Rl, int Rs, unsigned rmap, unsigned rmap2,
+                                   int to_lane, int64_t n4) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n4) return;
   const int U = H / 16;
@@ -431,13 +433,16 @@ __global__ void gru_lane_permute_k(const float* __restrict__ src, float* __restr
   const int j = ub * 16 + 4 * (lane >> 4);
   const int t = d == 0 ? s : T - 1 - s;
   const int rs = (int)((rmap >> (4 * k)) & 15u);
-  if (rs == 15) return;   // record not mapped
-  const int64_t so = (((int64_t)b * T + t) * ndir + d) * Rs * H + (int64_t)rs * H + j;
+  const int rs2 = dst2 ? (int)((rmap2 >> (4 * k)) & 15u) : 15;
+  if (rs == 15 && rs2 == 15) return;   // record not mapped
+  const int64_t row = (((int64_t)b * T + t) * ndir + d) * Rs * H + j;
   if (to_lane) {
     reinterpret_cast<float4*>(dst)[idx] =
-        b < B ? *reinterpret_cast<const float4*>(src + so) : make_float4(0.f, 0.f, 0.f, 0.f);
+        b < B ? *reinterpret_cast<const float4*>(src + row + (int64_t)rs * H) : make_float4(0.f, 0.f, 0.f, 0.f);
   } else if (b < B) {
-    *reinterpret_cast<float4*>(dst + so) = reinterpret_cast<const float4*>(src)[idx];
+    const float4 v = reinterpret_cast<const float4*>(src)[idx];
+    if (rs != 15) *reinterpret_cast<float4*>(dst + row + (int64_t)rs * H) = v;
+    if (rs2 != 15) *reinterpret_cast<float4*>(dst2 + row + (int64_t)rs2 * H) = v;
   }
 }
 
@@ -480,7 +485,24 @@ extern "C" int b2p_gru_lane_permute(const float* src, float* dst, int64_t B, int
   const int64_t n4 = b2p_gru16_lane_floats(B, T, H, ndir, Rl) / 4;
   if (n4 <= 0) return 0;
   hipLaunchKernelGGL(gru_lane_permute_k, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
-                     dst, (int)B, (int)T, (int)H, ndir, Rl, Rs, rmap, to_lane, n4);
+                     dst, (float*)nullptr, (int)B, (int)T, (int)H, ndir, Rl, Rs, rmap, 0xFFFFFFFFu, to_lane, n4);
+  B2P_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int b2p_gru_lane_unpack2(const float* src, float* dst, float* dst2, int64_t B, int64_t T, int64_t H,
+                                    int ndir, int Rl, int Rs, uint32_t rmap, uint32_t rmap2, b2p_stream_t stream) {
+  B2P_CHECK_ARG(src && dst && dst2, "gru_lane_unpack2: NULL pointer");
+  B2P_CHECK_ARG(H % 16 == 0 && Rl >= 1 && Rl <= 8 && Rs >= 1 && Rs <= 14, "gru_lane_unpack2: bad shape");
+  for (int k = 0; k < Rl; ++k) {
+    const uint32_t a = (rmap >> (4 * k)) & 15u, b = (rmap2 >> (4 * k)) & 15u;
+    B2P_CHECK_ARG((a == 15u || a < (uint32_t)Rs) && (b == 15u || b < (uint32_t)Rs),
+                  "gru_lane_unpack2: a map names a record past Rs");
+  }
+  const int64_t n4 = b2p_gru16_lane_floats(B, T, H, ndir, Rl) / 4;
+  if (n4 <= 0) return 0;
+  hipLaunchKernelGGL(gru_lane_permute_k, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
+                     dst, dst2, (int)B, (int)T, (int)H, ndir, Rl, Rs, rmap, rmap2, 0, n4);
   B2P_CHECK_LAUNCH();
   return 0;
 }

@@ -957,7 +957,15 @@ def gemm(M, N, K, A: Operand, B: Operand, C, ldc, c_off=0, cbs1=0, cbs2=0, nz1=1
                                                             + 2 * (C16b is not None)
                                                             + 4 * (residual is not None) + 4 * (beta != 0.0)
                                                             + (2 if aux16 is not None else 4 if aux is not None else 0))))
+    if _SKINNY32[0] and 32 in (M, N, K) and _lib.load().b2p_skinny32_form(ctypes.byref(d)):
+        _lib.check(_lib.load().b2p_skinny32(ctypes.byref(d), _st()), "b2p_skinny32")
+        return
     _lib.check(_lib.load().b2p_gemm(ctypes.byref(d), _st()), "b2p_gemm")
+
+
+# plain fp32-operand products with a 32-wide side (the CTC head's forward, input gradient and weight gradient)
+# run on the skinny kernels (csrc/skinny32.hip: same bits as gemm_kernel's); False (tests): gemm_kernel
+_SKINNY32 = [True]
 
 
 def _x3_role(A, B) -> str:
@@ -1494,18 +1502,35 @@ def _ln_bwd16(dy, x, g, mean, rstd, need_params=True, dx_accum=None, drop_p=0.0,
 @_prec_follow
 class _FrontEnd(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, day_idxs, day_weights, day_bias, taps):
+    def forward(ctx, x, day_idxs, day_weights, day_bias, taps, unfold=None):
         _chk(x, "front_end.x")
         _chk(day_weights, "front_end.day_weights")
         B, L, C = x.shape
         xs = torch.empty_like(x)
-        _lib.call("b2p_gauss_smooth", _p(x), _p(taps), taps.numel(), _p(xs), B, L, C, _st())
         z = torch.empty_like(x)
         s = torch.empty_like(x)
-        # z[b] = xs[b] @ W[day[b]] + bias[day[b]] ; s = softsign(z)   (einsum "btd,bdk->btk")
-        gemm(L, C, C, op(xs, 0, C, True, bs1=L * C), op(day_weights, 0, C, False, bs1=C * C, gather=day_idxs),
-             s, C, cbs1=L * C, nz1=B, bias=day_bias, biasbs1=C, bias_gather=day_idxs, pre_out=z,
-             act=ACT["softsign"])
+        if (_FRONT_FUSED[0] and bf16_mode() and C == 256 and C % 4 == 0 and taps.numel() <= 64 and B * L > 0
+                and day_bias is not None):
+            # one launch (csrc/front.hip), and with it the 16-bit source image the GRU's implicit-Unfold
+            # projection reads (_ImplicitUnfoldProj.source16), in the format that projection will ask for
+            half = bool(_state.fwd16)
+            s16 = None
+            if unfold is not None:
+                tail = (unfold[0] - unfold[1]) * C
+                # (_GRULayer.forward's conditions for the implicit projection)
+                if tail >= 0 and L % unfold[1] == 0 and unfold[0] % unfold[1] == 0:
+                    s16 = torch.empty(B * L * C + tail, device=x.device, dtype=torch.float16 if half else BF16)
+            _lib.call("b2p_front_fwd", _p(x), _p(taps), taps.numel(), _p(day_idxs), day_weights.shape[0],
+                      _p(day_weights), _p(day_bias), _p(xs), _p(z), _p(s), _p(s16), int(half),
+                      0 if s16 is None else s16.numel() - B * L * C, B, L, C, 2 if half else 0, _st())
+            if s16 is not None:
+                s._src16 = (s._version, s16)
+        else:
+            _lib.call("b2p_gauss_smooth", _p(x), _p(taps), taps.numel(), _p(xs), B, L, C, _st())
+            # z[b] = xs[b] @ W[day[b]] + bias[day[b]] ; s = softsign(z)   (einsum "btd,bdk->btk")
+            gemm(L, C, C, op(xs, 0, C, True, bs1=L * C), op(day_weights, 0, C, False, bs1=C * C, gather=day_idxs),
+                 s, C, cbs1=L * C, nz1=B, bias=day_bias, biasbs1=C, bias_gather=day_idxs, pre_out=z,
+                 act=ACT["softsign"])
         ctx.save_for_backward(xs, z, day_idxs, day_weights)
         ctx.n_days = day_weights.shape[0]
         return s
@@ -1528,14 +1553,22 @@ class _FrontEnd(torch.autograd.Function):
             colsum_batched(dz, B, L, C, per_b)
             dbias = torch.empty(ctx.n_days, 1, C, device=xs.device)
             _lib.call("b2p_day_reduce", _p(per_b), _p(day_idxs), B, ctx.n_days, C, _p(dbias), _st())
-        return None, None, dW, dbias, None
+        return None, None, dW, dbias, None, None
 
 
-def front_end(x, day_idxs, day_weights, day_bias, taps):
+# bf16 mode, C = 256: smoothing, day linear, softsign and the 16-bit source image in one launch (csrc/front.hip,
+# the same bits); False (tests): b2p_gauss_smooth, the gathered GEMM and, later, b2p_cast16_tail
+_FRONT_FUSED = [True]
+
+
+def front_end(x, day_idxs, day_weights, day_bias, taps, unfold=None):
     """b2p2t_model.py:150-159: permute -> GaussianSmoothing -> einsum(btd,bdk) + day_bias -> Softsign.
-    Returns the (B, L, 256) softsign output (the Unfold is implicit in the GRU layer-0 projection)."""
+    Returns the (B, L, 256) softsign output (the Unfold is implicit in the GRU layer-0 projection).
+    unfold = (kernel, stride) of the Unfolded the caller will wrap the output in: the fused forward then also
+    writes that view's 16-bit source image (_src16_of)."""
     with _fp32_if("front"):
-        return _FrontEnd.apply(x.contiguous(), day_idxs.to(torch.int64).contiguous(), day_weights, day_bias, taps)
+        return _FrontEnd.apply(x.contiguous(), day_idxs.to(torch.int64).contiguous(), day_weights, day_bias, taps,
+                               unfold)
 
 
 # =====================================================================================
@@ -1844,7 +1877,11 @@ class _ImplicitUnfoldProj:
     @staticmethod
     def source16(x, s, half):
         n_s, tail = s.B * s.L * s.C, (s.ktaps - s.stride) * s.C
-        s16 = torch.empty(n_s + tail, device=s.dev, dtype=torch.float16 if half else BF16)
+        dt = torch.float16 if half else BF16
+        s16 = _src16_of(x)
+        if s16 is not None and s16.dtype == dt and s16.numel() == n_s + tail:
+            return s16   # written by the fused front end, zero tail included
+        s16 = torch.empty(n_s + tail, device=s.dev, dtype=dt)
         _lib.call("b2p_cast16_tail", _p(x), _p(s16), n_s, n_s + tail, int(half), _st())
         return s16
 
@@ -1958,8 +1995,7 @@ class _GRULayer(torch.autograd.Function):
                                               _p(dh0), B, T, H, ndir, _st()))
             del doL
             # unpack: dgi = LN records (0, 1, 2), dgh = LN records (0, 1, 3)
-            _lib.call("b2p_gru_lane_permute", _p(dgL), _p(dgi), B, T, H, ndir, 4, 3, 0xF210, 0, _st())
-            _lib.call("b2p_gru_lane_permute", _p(dgL), _p(dgh), B, T, H, ndir, 4, 3, 0x2F10, 0, _st())
+            _lib.call("b2p_gru_lane_unpack2", _p(dgL), _p(dgi), _p(dgh), B, T, H, ndir, 4, 3, 0xF210, 0x2F10, _st())
             del dgL
         else:
             buf = _gru_launch(rec, True, (dout, whh_s, out, saved, h0, dgi, dgh, dh0), s, ctx.whh0)  # noqa: F841
@@ -2099,6 +2135,13 @@ def _b16_of(x):
 
 def _h16_of(x):
     t = getattr(x, "_h16", None)
+    return t[1] if t is not None and t[0] == x._version else None
+
+
+def _src16_of(x):
+    """The flat 16-bit image with its zero tail that _FrontEnd attached to its output (bf16, or fp16 under
+    forward_f16), while x is unchanged since."""
+    t = getattr(x, "_src16", None)
     return t[1] if t is not None and t[0] == x._version else None
 
 

@@ -78,7 +78,8 @@ class B2P2TModel(B2TModel):
         x, targets = batch
         day_idxs = batch.day_idxs
         taps = self.gaussian_smoother.taps()
-        s = Fn.front_end(x, day_idxs, self.day_weights, self.day_bias, taps)
+        s = Fn.front_end(x, day_idxs, self.day_weights, self.day_bias, taps,
+                         unfold=(self.config.unfolder_kernel_len, self.config.unfolder_stride_len))
         strided_inputs = Fn.Unfolded(s, self.config.unfolder_kernel_len, self.config.unfolder_stride_len)
         preprocessed_batch = batch.copy_and_change(input=strided_inputs)
         if hasattr(batch, "input_lens"):
